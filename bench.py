@@ -10,13 +10,23 @@ aligned UMEM (2048 B chunks, data at +256).  Each rank processes its own batch
 src/xsknf.c:1046-1100), so `scaling` is weak and `value` is the aggregate.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 1500|64|imix|jumbo]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and no more: it builds the primary
+workload, warms up, times the K steps and prints the line (`value`,
+`ms_per_step`, the whole-step roofline over the timed steps' own HIP events).
+--dump-outputs DIR also writes what the last timed step handed back (see
+dump_outputs).  Everything else -- the secondary workloads, the summing kernel
+alone, the read / step-floor probes, the CPU baseline, the RFC check, the root
+distribution at N > 1 and `c_host_multi` -- runs only with --full, and the
+options that shape those legs act only there.
 
 --gpus N > 1 without a torch.distributed.run environment starts the N ranks
 itself (one process per GPU, RCCL); the parent never touches the GPU.  On a box
 with fewer than N GPUs the ranks share the devices over gloo (a rehearsal of
 the N-rank path, marked `rehearsal` in the line).  Rank 0 prints ONE JSON line.
 
-Secondary workloads (timed after the primary, reported under `secondary`, each
+Secondary workloads (--full; timed after the primary, reported under `secondary`, each
 with its step fraction, kernel and committed PMC traffic): 64 B (config 2), a
 1M-frame IMIX batch (config 4's per-GPU shard), 9000 B jumbo frames in an
 unaligned UMEM (config 5), and config 4 -- the global 8,388,608-frame IMIX batch
@@ -26,7 +36,7 @@ at N = 1, exactly config 4's 8-way split at N = 8); the NIC-checksummed variants
 lane-kernel launch instead of 13: what a 64 B step costs without its launch's
 ramp and drain).
 
-At world 1 the line ends with `c_host_multi`: config 4 through the C host's
+At world 1 the --full line ends with `c_host_multi`: config 4 through the C host's
 multi-device calls over every visible device of this one process (span
 scatter, in-place steps, all-reduced counters; then the frames-only packed
 scatter and the results' return, checked byte for byte against one device's
@@ -127,7 +137,17 @@ def parse():
                         "launch starts while the previous one drains; needs >= 2 rotated batches)")
     p.add_argument("--kernel-steps", type=int, default=50,
                    help="launches of the summing kernel alone (records only), reported beside the step")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last one handed back as DIR/<name>.npy (dump_outputs)")
+    p.add_argument("--full", action="store_true",
+                   help="also run every leg beside the headline: --secondary workloads, --kernel-steps, the probes, "
+                        "the CPU baseline, the RFC check, the root distribution (N > 1) and c_host_multi; without "
+                        "it the options of those legs are ignored")
+    args = p.parse_args()
+    if not args.full:
+        args.secondary, args.cpu_seconds, args.kernel_steps = "", 0.0, 0
+        args.no_probes = args.no_c_host_multi = args.no_verify = args.no_root_scatter = True
+    return args
 
 
 # ---- rank launch --------------------------------------------------------------
@@ -272,6 +292,54 @@ def iterations_of_step(it: int, K: int) -> int:
     return 1 + ((it // K) & 1)
 
 
+DUMP_FRAMES = 1 << 20          # --dump-outputs: verdicts and checks of at most this many frames
+DUMP_WHOLE_FRAMES = 2048       # ... and every byte of at most this many of them,
+DUMP_WHOLE_BYTES = 4 << 20     # ... this many bytes at the most (16 MB as float32)
+
+
+def dump_outputs(path, rank, umem, descs, verdicts):
+    """--dump-outputs: what process_batch handed its caller in the last timed
+    step -- the batch's verdicts and its UMEM, whose frames now carry their
+    checks -- as float32 .npy files under `path` (rank r > 0: <name>.rank<r>.npy):
+
+      verdicts  the verdict of every frame (a batch of more than DUMP_FRAMES
+                frames: of a fixed, seeded, ascending sample of that many);
+      checks    the same frames' UDP check fields as the pass left them
+                (bytes 40-41 of the frame, little endian; -1 for a frame too
+                short to have one);
+      frames    every byte of a fixed, seeded sample of those frames after the
+                pass, one row per frame, -1 past the frame's end.
+
+    At most 24 MB.  The inputs are seeded, the warm-up ends on the same step of
+    the iteration schedule whatever its length, and the kernels sum integers:
+    the same arguments give the same files from run to run and build to build.
+    Returns the names written."""
+    os.makedirs(path, exist_ok=True)
+    n = int(descs.shape[0])
+    rng = np.random.default_rng(frames.SEED)
+    pick = np.sort(rng.choice(n, DUMP_FRAMES, replace=False)) if n > DUMP_FRAMES else np.arange(n)
+    d = descs[torch.from_numpy(pick).to(descs.device)]
+    start = (d[:, 0] & ((1 << 48) - 1)) + ((d[:, 0] >> 48) & 0xFFFF)
+    lens = d[:, 1] & 0xFFFFFFFF
+    at = (start + 40).clamp_(max=umem.numel() - 2)
+    checks = umem[at].to(torch.int32) | (umem[at + 1].to(torch.int32) << 8)
+    checks[lens < 42] = -1
+    width = int(lens.max())
+    m = max(1, min(pick.shape[0], DUMP_WHOLE_FRAMES, DUMP_WHOLE_BYTES // max(1, width)))
+    rows = torch.from_numpy(np.sort(rng.choice(pick.shape[0], m, replace=False))).to(descs.device)
+    col = torch.arange(width, device=descs.device)[None, :]
+    inside = col < lens[rows][:, None]
+    whole = umem[(start[rows][:, None] + col).clamp_(max=umem.numel() - 1)].to(torch.float32)
+    whole[~inside] = -1
+    arrays = {"verdicts": verdicts[torch.from_numpy(pick).to(verdicts.device)].to(torch.float32),
+              "checks": checks.to(torch.float32), "frames": whole}
+    names = []
+    for k, t in arrays.items():
+        names.append(k + (f".rank{rank}" if rank else "") + ".npy")
+        np.save(os.path.join(path, names[-1]), t.cpu().numpy())
+    return names
+
+
 def time_workload(name, args, world, rank, dev, seed, primary):
     length, layout, chunk, desc = WORKLOADS[name]
     lens_in, span = workload_lengths(name, args, world, rank)
@@ -340,6 +408,8 @@ def time_workload(name, args, world, rank, dev, seed, primary):
     it = [0]
     evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
            for _ in range(args.steps if nic else 0)]
+    dump = args.dump_outputs if primary else None
+    keep = [-1]   # --dump-outputs, NIC: the step whose changed checks stay until they are written out
 
     def step():
         j = it[0] % K
@@ -349,20 +419,23 @@ def time_workload(name, args, world, rank, dev, seed, primary):
         c.process_batch_ptr(umem_ptr, umem_size, descs_ptrs[j], n, v_ptrs[j], 0, streams[it[0] % S].cuda_stream)
         if nic:
             evs[it[0] % len(evs)][1].record(stream)
-            if restore[j][0].numel():
+            if restore[j][0].numel() and it[0] != keep[0]:
                 umem[restore[j][0]] = restore[j][1]   # this batch's changed checks, back as the NIC wrote them
         it[0] += 1
 
     # W untimed warmup steps, continued until at least --min-warmup-s of
     # warmup has run: measured on MI355X, 10 steps (3 ms) leave the step ~3 %
-    # slower than after 30 ms (clocks still ramping)
+    # slower than after 30 ms (clocks still ramping).  The extra steps come in
+    # whole periods of the schedule (2 K steps: every batch once with each
+    # iteration count; 10 at K = 1), so the timed steps visit the same batches
+    # with the same counts however long the warm-up took (--dump-outputs)
     t_w = time.perf_counter()
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
     warm_s = max(args.min_warmup_s, args.primary_warmup_s if primary else 0.0)
     while time.perf_counter() - t_w < warm_s:
-        for _ in range(10):
+        for _ in range(2 * K * -(-10 // (2 * K))):
             step()
         torch.cuda.synchronize()
     barrier(world)
@@ -370,6 +443,8 @@ def time_workload(name, args, world, rank, dev, seed, primary):
     ev1 = torch.cuda.Event(enable_timing=True)
     t0 = time.perf_counter()
     first = it[0]
+    if dump and nic:
+        keep[0] = first + args.steps - 1
     ev0.record(stream)
     for st in streams[1:]:
         st.wait_event(ev0)
@@ -391,8 +466,14 @@ def time_workload(name, args, world, rank, dev, seed, primary):
     # every rank's own step (HIP events) and wall time, and its bytes: a straggler
     # rank shows in the line (dist.per_rank), not only in the max
     per_rank = allgather_f64([step_ms, wall / args.steps * 1e3, float(bytes_len), float(n)], world)
-    if not nic:
-        # leave batch 0 as one -i 1 pass leaves it (the CPU leg checks it)
+    dumped = None
+    if dump:
+        j = (it[0] - 1) % K     # the last timed step's batch, before anything else touches it
+        dumped = dump_outputs(dump, rank, umem, descs[j * n:(j + 1) * n], verdicts[j * n:(j + 1) * n])
+        if nic and restore[j][0].numel():
+            umem[restore[j][0]] = restore[j][1]
+    if not nic and args.full:
+        # leave batch 0 as one -i 1 pass leaves it (the CPU leg and the RFC check read it)
         cs.process_batch_ptr(umem_ptr, umem_size, descs_ptrs[0], n, v_ptrs[0], 0, stream.cuda_stream)
         torch.cuda.synchronize()
 
@@ -455,7 +536,7 @@ def time_workload(name, args, world, rank, dev, seed, primary):
              "tile_pool": bool(cfg.kernel == 1 and cfg.window_chunks & 32),
              "frame_len_max": hint, "frame_len_mean": mean}
     return dict(name=name, desc=desc, n=n, K=K, lens=lens, bytes_len=bytes_len, step_ms=step_ms, stores=stores,
-                rfc=rfc,
+                rfc=rfc, dumped=dumped,
                 shape=shape,
                 step_ms_max=step_ms_max, per_rank=per_rank,
                 sum_ms=k_ms, single_kernel=single_kernel, family=family, wall_max=wall_max, counters=counters,
@@ -984,7 +1065,7 @@ def main():
         out = {
             "metric": METRIC, "value": round(value, 2), "unit": "GB/s checksummed",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "min_warmup_s": args.min_warmup_s,
-            "primary_warmup_s": args.primary_warmup_s,
+            "primary_warmup_s": args.primary_warmup_s, "full": args.full,
             "ms_per_step": round(step_s * 1e3, 4), "kernel_steps": args.kernel_steps,
             "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "u16 words summed in u32", "data": "synthetic",
@@ -996,6 +1077,8 @@ def main():
             "verdicts": {"drop": n_drop, "forward": n_fwd},
             "rfc_check": prim["rfc"],
         }
+        if prim["dumped"]:
+            out["outputs"] = {"dir": args.dump_outputs, "files": prim["dumped"]}
         if rehearsal:
             out["config"]["rehearsal"] = rehearsal
         if root_scatter is not None:

@@ -120,6 +120,63 @@ def test_lane_batch_workload_is_thirteen_batches():
     assert lens.shape[0] == 13 * 1024 and span is None and int(lens.max()) == 64
 
 
+def test_plain_run_switches_every_other_leg_off(monkeypatch):
+    """Without --full only the headline runs, whatever the other legs' options
+    say; with it they act as given."""
+    import sys
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2",
+                                      "--secondary", "64", "--cpu-seconds", "3"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    assert (a.secondary, a.cpu_seconds, a.kernel_steps) == ("", 0.0, 0)
+    assert a.no_probes and a.no_c_host_multi and a.no_verify and a.no_root_scatter
+    monkeypatch.setattr(sys, "argv", sys.argv + ["--full"])
+    a = bench.parse()
+    assert (a.secondary, a.cpu_seconds, a.kernel_steps, a.full) == ("64", 3.0, 50, True)
+    assert not (a.no_probes or a.no_c_host_multi or a.no_verify or a.no_root_scatter)
+
+
+def test_dump_outputs_writes_the_pass_as_float32(tmp_path, monkeypatch):
+    """--dump-outputs: verdicts, check fields (-1 for a frame too short to have
+    one) and whole frames (-1 past a frame's end) of the batch as float32; a
+    batch over the limits is sampled, the same frames every time."""
+    import torch
+    from xsknf_amd import frames
+    b = frames.unaligned_batch(300, "imix", seed=71)
+    b.descs["len"][5] = 30
+    umem = torch.from_numpy(b.umem)
+    descs = torch.from_numpy(b.descs.view(np.int64).reshape(-1, 2).copy())
+    verdicts = torch.arange(300, dtype=torch.int32) % 3 - 1
+    offs = b.frame_offsets().astype(np.int64)
+    lens = b.descs["len"].astype(np.int64)
+    want_c = (b.umem[offs + 40].astype(np.int32) | (b.umem[offs + 41].astype(np.int32) << 8)).astype(np.float32)
+    want_c[5] = -1
+
+    assert bench.dump_outputs(str(tmp_path / "a"), 0, umem, descs, verdicts) == [
+        "verdicts.npy", "checks.npy", "frames.npy"]
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in ("verdicts", "checks", "frames")}
+    assert all(x.dtype == np.float32 for x in got.values())
+    assert np.array_equal(got["verdicts"], verdicts.numpy().astype(np.float32))
+    assert np.array_equal(got["checks"], want_c)
+    assert got["frames"].shape == (300, 1500)
+    for i in (0, 5, 299):
+        assert np.array_equal(got["frames"][i, :lens[i]], b.frame(i).astype(np.float32))
+        assert (got["frames"][i, lens[i]:] == -1).all()
+
+    monkeypatch.setattr(bench, "DUMP_FRAMES", 100)
+    monkeypatch.setattr(bench, "DUMP_WHOLE_FRAMES", 10)
+    for d in ("b", "c"):
+        assert bench.dump_outputs(str(tmp_path / d), 1, umem, descs, verdicts) == [
+            "verdicts.rank1.npy", "checks.rank1.npy", "frames.rank1.npy"]
+    s = {k: np.load(tmp_path / "b" / f"{k}.rank1.npy") for k in ("verdicts", "checks", "frames")}
+    assert s["verdicts"].shape == (100,) and s["checks"].shape == (100,) and s["frames"].shape[0] == 10
+    for k, x in s.items():
+        assert np.array_equal(x, np.load(tmp_path / "c" / f"{k}.rank1.npy"))
+    # the sample is ascending and without repeats: it is a subsequence of the whole
+    pick = np.sort(np.random.default_rng(frames.SEED).choice(300, 100, replace=False))
+    assert np.array_equal(s["checks"], want_c[pick])
+
+
 _LEG_CHILD = r"""
 import os, sys, time
 sys.path.insert(0, {root!r})

@@ -9,7 +9,9 @@
   cuda:0, the HIP kernel run on the shards each rank received;
 * `bench.py --gpus N` (N = 2, 4) started by hand on a one-GPU box starts its
   N ranks itself (gloo rehearsal), reports n_gpus = N, splits config 4 N ways
-  and delivers every frame of the root distribution.
+  and delivers every frame of the root distribution;
+* a plain `bench.py --gpus 1` times the headline alone, and --dump-outputs
+  writes the last timed step's results, equal to the oracle's.
 
 Processes are started from the forkserver of tests/conftest.py, never from this
 (GPU-initialised) process.
@@ -386,8 +388,8 @@ def test_bench_gpus_n_starts_its_ranks(dev, clean_ctx, world):
         env["XSKNF_BENCH_BACKEND"] = "gloo"
     c4 = 131072
     cmd = [sys.executable, "bench.py", "--gpus", str(world), "--steps", "3", "--warmup", "1", "--frames", "65536",
-           "--secondary", "config4", "--config4-frames", str(c4), "--cpu-seconds", "0", "--kernel-steps", "0",
-           "--min-warmup-s", "0"]
+           "--full", "--secondary", "config4", "--config4-frames", str(c4), "--cpu-seconds", "0",
+           "--kernel-steps", "0", "--min-warmup-s", "0"]
     with clean_ctx.Pool(1) as pool:
         rc, out, err = pool.apply(_run, (cmd, env, 400))
     assert rc == 0, err[-3000:]
@@ -432,8 +434,8 @@ def test_rccl_collectives_on_one_gpu(dev, clean_ctx):
     env.pop("XSKNF_BENCH_BACKEND", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr=127.0.0.1", f"--master-port={port}", "bench.py", "--gpus", "1", "--steps", "3",
-           "--warmup", "1", "--frames", "65536", "--secondary", "", "--cpu-seconds", "0", "--kernel-steps", "0",
-           "--min-warmup-s", "0", "--no-probes"]
+           "--warmup", "1", "--frames", "65536", "--full", "--secondary", "", "--cpu-seconds", "0",
+           "--kernel-steps", "0", "--min-warmup-s", "0", "--no-probes"]
     with clean_ctx.Pool(1) as pool:
         rc, out, err = pool.apply(_run, (cmd, env, 400))
     assert rc == 0, err[-3000:]
@@ -445,3 +447,43 @@ def test_rccl_collectives_on_one_gpu(dev, clean_ctx):
     assert line["root_scatter"]["frames_total"] == 65536
     assert line["root_scatter"]["vs_single_gpu"]["match"] is True
     assert line["root_scatter"]["rfc_check"]["violations"] == 0
+
+
+def test_plain_bench_times_its_steps_and_dumps_the_last_one(dev, clean_ctx, tmp_path):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` runs the headline alone
+    (no secondary workload, CPU baseline, probe, RFC check or c_host_multi), N
+    is the number of timed steps, and --dump-outputs writes the last timed
+    step's verdicts, checks and frames as float32: equal to the oracle's pass
+    with that step's iteration count over the same seeded batch."""
+    import bench
+    n, steps, warmup = 2048, 3, 1
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+           "--frames", str(n), "--rotate", "1", "--primary-warmup-s", "0", "--min-warmup-s", "0",
+           "--dump-outputs", str(tmp_path)]
+    with clean_ctx.Pool(1) as pool:
+        rc, so, err = pool.apply(_run, (cmd, dict(os.environ), 300))
+    assert rc == 0, err[-3000:]
+    js = [ln for ln in so.splitlines() if ln.startswith("{")]
+    assert len(js) == 1, so
+    line = json.loads(js[0])
+    assert line["steps"] == steps and line["full"] is False
+    assert line["ms_per_step"] > 0 and line["higher_is_better"] is True and line["unit"] == "GB/s checksummed"
+    assert abs(line["value"] - n * 1500 / (line["ms_per_step"] / 1e3) / 1e9) <= 0.01 + 1e-3 * line["value"]
+    assert line["secondary"] == {} and line["cpu_baseline"] is None and line["rfc_check"] is None
+    assert "c_host_multi" not in line and "root_scatter" not in line
+    assert line["roofline"]["probes"] is None and line["roofline"]["summing_kernel_alone"] is None
+    assert sorted(line["outputs"]["files"]) == ["checks.npy", "frames.npy", "verdicts.npy"]
+
+    umem, descs, _ = frames.device_batch(n, 1500, layout="aligned", chunk=frames.CHUNK, seed=frames.SEED, device=dev)
+    host = umem.cpu().numpy()
+    hd = descs.cpu().numpy().view(frames.DESC_DTYPE).reshape(-1).copy()
+    want_v = O.c_process_batch(host, hd, iters=bench.iterations_of_step(warmup + steps - 1, 1))
+    offs = frames.HostBatch(host, hd, "aligned").frame_offsets().astype(np.int64)
+    want_c = host[offs + 40].astype(np.int32) | (host[offs + 41].astype(np.int32) << 8)
+    got = {k: np.load(tmp_path / f"{k}.npy") for k in ("verdicts", "checks", "frames")}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert np.array_equal(got["verdicts"], want_v.astype(np.float32))
+    assert np.array_equal(got["checks"], want_c.astype(np.float32))
+    assert got["frames"].shape == (n, 1500)          # n <= DUMP_WHOLE_FRAMES: every frame, in order
+    assert np.array_equal(got["frames"], host.reshape(n, frames.CHUNK)[:, frames.HEADROOM:frames.HEADROOM + 1500])
+

@@ -349,6 +349,7 @@ def test_veth_config1_is_bit_exact():
 
 @pytest.mark.parametrize("extra", [("--two-phase",), ("--two-phase", "--poll"), ("--poll",)],
                          ids=["two-phase", "two-phase-poll", "poll"])
+@pytest.mark.skipif(not _veth_available(), reason="needs root, netns and tools/build/xsk_veth (make tools)")
 def test_veth_config1_hooks_and_poll(extra):
     """Real AF_XDP sockets: the two-phase hook keeps a batch in flight across worker
     passes, and with poll() a pass never blocks while one is out (the last batch

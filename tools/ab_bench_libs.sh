@@ -8,7 +8,7 @@ TAG=$1; LIBS=$2; SEC=${3:-imix}; REPS=${4:-3}
 mkdir -p gpurun_out/ab
 for rep in $(seq "$REPS"); do
   for L in $LIBS; do
-    XSKNF_GPU_LIB=$PWD/$L/libxsknf_gpu.so timeout -k 10 300 python bench.py --secondary "$SEC" --cpu-seconds 0 \
+    XSKNF_GPU_LIB=$PWD/$L/libxsknf_gpu.so timeout -k 10 300 python bench.py --full --secondary "$SEC" --cpu-seconds 0 \
       --no-probes 2> gpurun_out/ab/${TAG}_bench.err | grep '^{' | sed "s|^{|{\"lib\": \"$L\", \"rep\": $rep, |" \
       >> gpurun_out/ab/${TAG}_bench.jsonl || { tail -20 gpurun_out/ab/${TAG}_bench.err; exit 1; }
   done

@@ -6,7 +6,7 @@ set -o pipefail
 OUT=gpurun_out/${1:-r05jw}; mkdir -p "$OUT"
 run() {   # case args...
   local c=$1; shift
-  timeout -k 10 300 python bench.py --cpu-seconds 0 "$@" 2>>"$OUT/err" | grep '^{' \
+  timeout -k 10 300 python bench.py --full --cpu-seconds 0 "$@" 2>>"$OUT/err" | grep '^{' \
     | sed "s|^{|{\"case\": \"$c\", \"rep\": $rep, |" >> "$OUT/ab.jsonl"
 }
 CASES=${2:-probes}

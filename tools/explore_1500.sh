@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$R/gpurun_out/${1:-explore_1500}
 mkdir -p "$OUT"
 cd "$R"
-[ -n "$SKIP_PROBE" ] || timeout -k 10 240 env HBM_PROBE_VERBOSE=1 python bench.py --secondary "" --cpu-seconds 0 > "$OUT/bench.json" \
+[ -n "$SKIP_PROBE" ] || timeout -k 10 240 env HBM_PROBE_VERBOSE=1 python bench.py --full --secondary "" --cpu-seconds 0 > "$OUT/bench.json" \
     2> "$OUT/bench.err" || { tail "$OUT/bench.err"; exit 1; }
 [ -n "$SKIP_PROBE" ] || grep hbm_probe "$OUT/bench.err"
 timeout -k 10 400 env XSKNF_GPU_LIB=$R/build/ab/libxsknf_gpu.so python tools/tune.py --workload 1500 \

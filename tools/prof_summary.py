@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-kernel durations of one bench.py run under rocprofv3 --kernel-trace
+"""Per-kernel durations of one bench.py --full run under rocprofv3 --kernel-trace
 (tools/prof_stats.sh), split the way the bench dispatches them:
 
   * the step's kernels (warm-up + timed steps, and a scatter_checks launch per

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """HBM traffic per hot-path step from rocprofv3 --pmc passes (tools/prof_pmc.sh).
 
-A bench.py run dispatches the step's kernel (warm-up + timed steps) and then,
+A bench.py --full run dispatches the step's kernel (warm-up + timed steps) and then,
 for the split kernel, the same kernel in records-only mode (the summing pass
 alone: --kernel-steps launches at the end).  Counter calibration (gfx950,
 MI355X_MICROARCH.md "HBM"; checked on tools/hbm_probe over known byte counts,
