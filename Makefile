@@ -5,6 +5,9 @@ HIPFLAGS ?= -O3 -std=c++17 -fPIC -Wall -Wno-inline-asm -fvisibility=hidden --off
 LIBDIR := xsknf_amd/lib
 LIB := $(LIBDIR)/libxsknf_gpu.so
 SRCS := xsknf_amd/csrc/checksummer.hip xsknf_amd/csrc/host_path.hip xsknf_amd/csrc/multi.hip xsknf_amd/csrc/shard_plan.cpp
+# every header the device code may include: checksummer.hip is one translation
+# unit over csum_device.h and the kernel_*.h families
+GPUHDRS := include/xsknf_gpu.h include/xsknf.h $(wildcard xsknf_amd/csrc/*.h)
 # RCCL for the multi-device calls (xsknf_gpu_multi_*)
 GPULIBS := -L/opt/rocm/lib -lrccl
 
@@ -23,7 +26,7 @@ ASM := build/asm/checksummer-gfx950.s
 # The library is kept only if the device code passes tools/check_inflight.py:
 # no instruction may name a register of an inline-asm load before its counted
 # s_waitcnt (the compiler does not know those registers are still in flight).
-$(LIB): $(SRCS) include/xsknf_gpu.h xsknf_amd/csrc/checksummer_internal.h xsknf_amd/csrc/checksummer_ab.h tools/check_inflight.py Makefile
+$(LIB): $(SRCS) $(GPUHDRS) tools/check_inflight.py Makefile
 	@mkdir -p $(LIBDIR) build/asm
 	$(HIPCC) $(HIPFLAGS) --cuda-device-only -S -o $(ASM) xsknf_amd/csrc/checksummer.hip
 	python3 tools/check_inflight.py $(ASM)
@@ -89,7 +92,7 @@ $(CTXLAT): tools/ctx_latency.c $(LIB)
 # XSKNF_GPU_LIB=build/ab/libxsknf_gpu.so selects it).  Not the product.
 ABLIB := build/ab/libxsknf_gpu.so
 ab: $(ABLIB)
-$(ABLIB): $(SRCS) include/xsknf_gpu.h xsknf_amd/csrc/checksummer_internal.h xsknf_amd/csrc/checksummer_ab.h tools/check_inflight.py Makefile
+$(ABLIB): $(SRCS) $(GPUHDRS) tools/check_inflight.py Makefile
 	@mkdir -p build/ab
 	$(HIPCC) $(HIPFLAGS) -DXSKNF_AB --cuda-device-only -S -o build/ab/checksummer-gfx950.s xsknf_amd/csrc/checksummer.hip
 	python3 tools/check_inflight.py build/ab/checksummer-gfx950.s
@@ -99,14 +102,14 @@ $(ABLIB): $(SRCS) include/xsknf_gpu.h xsknf_amd/csrc/checksummer_internal.h xskn
 # samples (tools/timeline.py).  Not the product.
 TLLIB := build/tl/libxsknf_gpu.so
 tl: $(TLLIB)
-$(TLLIB): $(SRCS) include/xsknf_gpu.h xsknf_amd/csrc/checksummer_internal.h xsknf_amd/csrc/checksummer_ab.h tools/check_inflight.py Makefile
+$(TLLIB): $(SRCS) $(GPUHDRS) tools/check_inflight.py Makefile
 	@mkdir -p build/tl
 	$(HIPCC) $(HIPFLAGS) -DXSKNF_TIMELINE $(TLFLAGS) --cuda-device-only -S -o build/tl/checksummer-gfx950.s xsknf_amd/csrc/checksummer.hip
 	python3 tools/check_inflight.py build/tl/checksummer-gfx950.s
 	$(HIPCC) $(HIPFLAGS) -DXSKNF_TIMELINE $(TLFLAGS) -shared -o $@ $(SRCS) $(GPULIBS)
 
 # keep the device assembly for inspection (VGPRs, instruction mix)
-asm: $(SRCS)
+asm: $(SRCS) $(GPUHDRS)
 	@mkdir -p build/asm
 	$(HIPCC) $(HIPFLAGS) --cuda-device-only -S -o $(ASM) xsknf_amd/csrc/checksummer.hip
 
@@ -127,6 +130,6 @@ clean:
 # recorded instead of faulting (tools/guard_run.py).  Not the product.
 GDLIB := build/guard/libxsknf_gpu.so
 guard: $(GDLIB)
-$(GDLIB): $(SRCS) include/xsknf_gpu.h xsknf_amd/csrc/checksummer_internal.h Makefile
+$(GDLIB): $(SRCS) $(GPUHDRS) Makefile
 	@mkdir -p build/guard
 	$(HIPCC) $(HIPFLAGS) -DXSKNF_GUARD -shared -o $@ $(SRCS) $(GPULIBS)

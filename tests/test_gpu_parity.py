@@ -888,7 +888,7 @@ def test_concurrent_streams(dev):
     runs one stream per worker): every one bit-exact.  The scatter pass's
     per-launch record counters (64 sets) are reused by launches 64 apart:
     with more than 64 launches queued at once, a reused set must make the
-    pass scan, never skip (g_rec_count in checksummer.hip)."""
+    pass scan, never skip (g_rec_count in csum_device.h)."""
     nstreams = 24
     jobs = []
     for i in range(nstreams):
@@ -1112,3 +1112,139 @@ def test_pool_units_cover_every_frame(dev, shape, n):
     torch.cuda.synchronize()
     assert np.array_equal(v.cpu().numpy(), ov)
     assert np.array_equal(umem.cpu().numpy(), ou)
+
+
+# ---- where a check's 64-byte sector lies: a directed batch ---------------------
+
+_SECTOR_LENS = {"short": (60, 64, 100, 128), "long": (60, 64, 128, 600, 2100)}
+_SECTOR_CLASSES = ("inside", "before_frame", "past_frame", "past_window", "split")
+
+
+def _sector_batch(kind):
+    """Every frame start modulo 64 x every ihl nibble x the lengths of `kind`,
+    in the unaligned (base | off << 48) layout; payload and old checks random."""
+    lens_set = _SECTOR_LENS[kind]
+    s64, ihl, ln = np.meshgrid(np.arange(64), np.arange(16), np.asarray(lens_set), indexing="ij")
+    s64, ihl, ln = s64.ravel().astype(np.int64), ihl.ravel().astype(np.int64), ln.ravel().astype(np.int64)
+    n = ln.size
+    slot = (ln + 63 + 63) // 64 * 64                    # room for the frame at any start modulo 64
+    starts = 64 + np.cumsum(slot) - slot + s64
+    rng = np.random.default_rng(950)
+    umem = rng.integers(0, 256, size=int(starts[-1] + ln[-1]) + 80, dtype=np.uint8)
+    h = frames.headers(ln, rng.integers(0, 256, size=n))
+    h[:, 14] = 0x40 | ihl
+    umem[starts[:, None] + np.arange(frames.HDR_LEN)[None, :]] = h
+    offs = np.minimum(np.arange(n) % 256, starts)
+    descs = np.zeros(n, dtype=frames.DESC_DTYPE)
+    descs["addr"] = (starts - offs).astype(np.uint64) | (offs.astype(np.uint64) << np.uint64(frames.OFFSET_SHIFT))
+    descs["len"] = ln
+    return frames.HostBatch(umem, descs, "unaligned")
+
+
+def _sector_classes(b, wbytes):
+    """From the inputs alone: per summed frame (IPv4, UDP, check inside the
+    frame), where the 64-byte sector of its check lies for a header window of
+    `wbytes` from the frame's 16-byte aligned start; and whether the frame ends
+    inside that window."""
+    start = b.frame_offsets().astype(np.int64)
+    ln = b.descs["len"].astype(np.int64)
+    u = 14 + 4 * (b.umem[start + 14].astype(np.int64) & 15)
+    summed = (ln >= 34) & (u + 8 <= ln)
+    ck = start + u + 6
+    sec = ck & ~np.int64(63)
+    c0 = start & ~np.int64(15)
+    split = (ck & 63) == 63
+    before = ~split & (sec < start)
+    past_frame = ~split & ~before & (sec + 64 > start + ln)
+    past_window = ~split & ~before & ~past_frame & (sec + 64 > c0 + wbytes)
+    inside = ~split & ~before & ~past_frame & ~past_window
+    cls = dict(zip(_SECTOR_CLASSES, (inside, before, past_frame, past_window, split)))
+    return {k: v & summed for k, v in cls.items()}, summed & (start + ln <= c0 + wbytes)
+
+
+_sector_cache = {}
+
+
+def _sector_case(kind):
+    if kind not in _sector_cache:
+        b = _sector_batch(kind)
+        _sector_cache[kind] = (b,) + run_oracle(b, iters=2, action=O.REDIRECT, nif=3, ingress=1)
+    return _sector_cache[kind]
+
+
+_LANE = [(1, 5, 2, 0), (1, 5, 2, 0, None, 0, 1024)]
+_SPLIT = [(16, 2, 2, 0, None, 1, 24), (16, 2, 2, 0, None, 1, 56), (16, 3, 2, 0, None, 1, 52)]
+_GROUP = [(32, 3, 2, 0), (64, 2, 4, 0)]
+_SECTOR_SHAPES = ([s[:4] + (m,) + s[5:] for s in _LANE + _GROUP for m in (1, 5, 2)] +
+                  [s[:4] + (m,) + s[5:] for s in _SPLIT for m in (1, 5, 2, 18)])
+
+
+@pytest.mark.parametrize("shape", _SECTOR_SHAPES, ids=[_shape_id(s) for s in _SECTOR_SHAPES])
+def test_check_sector_positions(dev, shape):
+    """What becomes of a finished check, by where its 64-byte sector lies: wholly
+    inside frame and header window (written as the sector), starting before the
+    frame, ending past the frame's end, ending past the window, or the check
+    split across two sectors (each written as 2 bytes) -- every frame start
+    modulo 64 x every ihl x lengths that end inside the window (the lane kernel,
+    the split kernel's phase A) and well past it (phase C, the group kernels'
+    later passes), under in-line sector, in-line 2-byte and deferred stores.
+    Every verdict and UMEM byte equal to the reference's own function."""
+    import ctypes
+    from xsknf_amd import _lib
+    lib = _lib.load()
+    lane, split = shape[0] == 1, len(shape) > 5 and shape[5] == 1
+    b, ou, ov = _sector_case("short" if lane else "long")
+    # the window: the lane kernel's 5 chunks, the split kernel's W (window field & 15);
+    # a group kernel has none, and its whole-sector store needs only a frame of one
+    # pass (lanes x chunks x 16 bytes): "past the window" is a frame longer than that
+    wbytes = 16 * (shape[1] if lane else shape[6] & 15) if lane or split else 16 * shape[0] * shape[1]
+    cls, in_window = _sector_classes(b, wbytes)
+    if not lane and not split:
+        start, ln = b.frame_offsets().astype(np.int64), b.descs["len"].astype(np.int64)
+        longer = cls["inside"] & (start + ln > (start & ~np.int64(15)) + wbytes)
+        cls["inside"], cls["past_window"] = cls["inside"] & ~longer, cls["past_window"] | longer
+    counts = {k: int(v.sum()) for k, v in cls.items()}
+    print(_shape_id(shape), b.n, "frames", counts)
+    assert all(counts.values()), counts           # a condition on the fixture
+    if split:                                     # phase A and phase C both finish frames of every in-frame class
+        for k in ("inside", "past_frame", "split"):
+            assert (cls[k] & in_window).any() and (cls[k] & ~in_window).any(), k
+    umem = torch.from_numpy(b.umem).to(dev)
+    descs = torch.from_numpy(b.descs.view(np.uint8).reshape(-1, 16).copy()).to(dev)
+    v = torch.empty(b.n, dtype=torch.int32, device=dev)
+    rc = lib.xsknf_gpu_checksum_batch_cfg(
+        ctypes.c_void_p(umem.data_ptr()), umem.numel(), ctypes.c_void_p(descs.data_ptr()), b.n, 1,
+        ctypes.byref(_lib.CsumOpts(2, O.REDIRECT, 3, 0)), ctypes.c_void_p(v.data_ptr()),
+        ctypes.byref(launch_cfg(shape)), None)
+    assert rc == 0
+    gv, gu = _results(v, umem)
+    assert np.array_equal(gv, ov)
+    assert np.array_equal(gu, ou)
+
+
+@pytest.mark.parametrize("change", [dict(ring=1), dict(fused=-1), dict(fused=64), dict(bpc=-1), dict(bpc=65),
+                                    dict(window=57), dict(kernel=0, lpf=1, nch=5, window=2048),
+                                    dict(lpf=3), dict(kernel=0, window=0, lpf=32, nch=3, u=3)],
+                         ids=lambda c: "-".join(f"{k}{v}" for k, v in c.items()))
+def test_bad_launch_cfgs_are_refused(dev, change):
+    """A launch cfg outside what run() serves -- lds_ring set, fused_stores or
+    blocks_per_cu out of range, an unknown window field or (lanes, chunks,
+    frames per group) -- is -EINVAL and nothing is launched: the UMEM of a
+    one-frame batch stays as it was."""
+    import ctypes
+    import errno
+    from xsknf_amd import _lib
+    lib = _lib.load()
+    c = dict(lpf=16, nch=2, u=2, bpc=4, ring=0, fused=18, kernel=1, window=56)
+    c.update(change)
+    b = frames.unaligned_batch(1, 600, seed=3)
+    umem = torch.from_numpy(b.umem).to(dev)
+    descs = torch.from_numpy(b.descs.view(np.uint8).reshape(-1, 16).copy()).to(dev)
+    v = torch.full((1,), 77, dtype=torch.int32, device=dev)
+    cfg = _lib.LaunchCfg(c["lpf"], c["nch"], c["u"], c["bpc"], c["ring"], c["fused"], c["kernel"], c["window"])
+    rc = lib.xsknf_gpu_checksum_batch_cfg(
+        ctypes.c_void_p(umem.data_ptr()), umem.numel(), ctypes.c_void_p(descs.data_ptr()), 1, 0,
+        ctypes.byref(_lib.CsumOpts(1, O.REDIRECT, 1, 0)), ctypes.c_void_p(v.data_ptr()), ctypes.byref(cfg), None)
+    assert rc == -errno.EINVAL
+    gv, gu = _results(v, umem)
+    assert np.array_equal(gu, b.umem) and gv[0] == 77

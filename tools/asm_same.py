@@ -2,12 +2,16 @@
 """Are the product kernels' instruction streams the same as at another commit?
 
 Builds the device assembly of xsknf_amd/csrc/checksummer.hip as it was at REV
-(into a scratch directory) and compares it kernel by kernel with the current
-product assembly (`make asm` -> build/asm/checksummer-gfx950.s), ignoring
-labels, comments and directives.  Use it to tell whether profiles recorded at
-REV still describe the product's kernels:
+(into a scratch directory, with every header under xsknf_amd/csrc/ and include/
+that REV has) and compares it kernel by kernel with the current product
+assembly (`make asm` -> build/asm/checksummer-gfx950.s), ignoring labels,
+comments and directives.  Use it to tell whether profiles recorded at REV still
+describe the product's kernels:
 
-    python3 tools/asm_same.py <rev> [--diff]
+    python3 tools/asm_same.py <rev> [multi.hip | host_path.hip] [--diff]
+
+With a second source file named, its kernels are compared instead (both sides
+compiled into the scratch directory).
 
 --diff prints the instruction diff of every kernel that is not identical
 (a renamed twin is matched by name with its template arguments removed).
@@ -28,13 +32,25 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-inline-asm", "-fvisibility=hidden", "--offload-arch=gfx950",
          "--cuda-device-only", "-S"]
-FILES = ["xsknf_amd/csrc/checksummer.hip", "xsknf_amd/csrc/checksummer_internal.h", "include/xsknf_gpu.h"]
+CSRC = "xsknf_amd/csrc"
+SOURCES = ["checksummer.hip", "multi.hip", "host_path.hip"]
+
+
+def files_at(rev, source):
+    """The source and every header it may include, as REV has them."""
+    ls = subprocess.run(["git", "-C", ROOT, "ls-tree", "-r", "--name-only", rev, CSRC + "/", "include/"], check=True,
+                        stdout=subprocess.PIPE, text=True).stdout.split()
+    return [f"{CSRC}/{source}"] + [f for f in ls if f.endswith(".h")]
+
+
+def compile_asm(cwd, source, out):
+    subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, "-Iinclude", "-o", out, f"{CSRC}/{source}"], cwd=cwd, check=True)
 
 
 def kernels(path):
     out, cur = {}, None
     for line in open(path):
-        m = re.match(r"^(_ZN9xsknf_gpu\w+):", line)
+        m = re.match(r"^(_ZN(?:9xsknf_gpu|12_GLOBAL__N_1)\w+):", line)   # (multi.hip: an unnamed namespace)
         if m:
             cur = m.group(1)
             out[cur] = []
@@ -75,19 +91,24 @@ def main():
         return vs_ab()
     args = [a for a in sys.argv[1:] if a != "--diff"]
     show = "--diff" in sys.argv[1:]
-    if len(args) != 1:
+    if len(args) not in (1, 2) or (len(args) == 2 and os.path.basename(args[1]) not in SOURCES):
         raise SystemExit(__doc__)
     rev = args[0]
-    cur = os.path.join(ROOT, "build", "asm", "checksummer-gfx950.s")
-    subprocess.run(["make", "-C", ROOT, "asm"], check=True, stdout=subprocess.DEVNULL)
+    source = os.path.basename(args[1]) if len(args) == 2 else SOURCES[0]
     with tempfile.TemporaryDirectory() as d:
-        for f in FILES:
+        if source == SOURCES[0]:
+            cur = os.path.join(ROOT, "build", "asm", "checksummer-gfx950.s")
+            subprocess.run(["make", "-C", ROOT, "asm"], check=True, stdout=subprocess.DEVNULL)
+        else:
+            cur = os.path.join(d, "cur.s")
+            compile_asm(ROOT, source, cur)
+        for f in files_at(rev, source):
             os.makedirs(os.path.join(d, os.path.dirname(f)), exist_ok=True)
             with open(os.path.join(d, f), "wb") as fh:
                 fh.write(subprocess.run(["git", "-C", ROOT, "show", f"{rev}:{f}"], check=True,
                                         stdout=subprocess.PIPE).stdout)
         old = os.path.join(d, "old.s")
-        subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, "-Iinclude", "-o", old, FILES[0]], cwd=d, check=True)
+        compile_asm(d, source, old)
         a, b = kernels(old), kernels(cur)
     same, bad = 0, 0
     for k in sorted(set(a) & set(b)):

@@ -2,7 +2,7 @@
 
 The reference (FedeParola/xsknf) calls `xsknf_packet_processor()` once per
 AF_XDP frame; here a whole rx batch is checksummed by one gfx950 kernel
-(`xsknf_amd/csrc/checksummer.hip`) behind the C ABI of `include/xsknf_gpu.h`.
+(`xsknf_amd/csrc/checksummer.hip` and the `kernel_*.h` it includes) behind the C ABI of `include/xsknf_gpu.h`.
 """
 from .checksummer import (ACTION_DROP, ACTION_REDIRECT, Checksummer, ChecksummerOptions, HostPath,
                           parse_command_line)

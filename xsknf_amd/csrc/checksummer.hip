@@ -1,4 +1,9 @@
-// checksummer.hip -- gfx950 kernels for the xsknf checksummer per-packet path.
+// checksummer.hip -- gfx950 kernels for the xsknf checksummer per-packet path:
+// one translation unit.  The device code is in csum_device.h (shared helpers)
+// and one header per kernel family -- kernel_group.h (register), kernel_lane.h,
+// kernel_split.h, kernel_scatter.h, kernel_resident.h; this file keeps the host
+// side: error text, grid sizing, the launchers, the Variant table, default_cfg,
+// prepare, run and the C API.
 //
 // Reference semantics: examples/checksummer/checksummer_user.c:30-112
 // (xsknf_packet_processor), applied to every descriptor of an rx batch as the
@@ -59,1980 +64,14 @@
 #include "../../include/xsknf_gpu.h"
 #include "checksummer_internal.h"
 
-namespace xsknf_gpu {
-
-constexpr int kWave = 64;
-constexpr int kBlock = 256;
-constexpr int kWavesPerBlock = kBlock / kWave;
-constexpr int kHdrChunks = 7;    // window chunks 0..6 hold frame bytes [0, 97) at any 16-B phase
-constexpr int kSlotBytes = 128;  // register kernel: per-group LDS header window
-
-// ---- small device helpers ---------------------------------------------------
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) uint8_t lds_u8;
-
-__device__ __forceinline__ uint64_t umem_offset(uint64_t addr) {
-  return (addr & XSKNF_GPU_UNALIGNED_BUF_ADDR_MASK) + (addr >> XSKNF_GPU_UNALIGNED_BUF_OFFSET_SHIFT);
-}
-
-__device__ __forceinline__ void compiler_barrier() {
-  __builtin_amdgcn_wave_barrier();
-  asm volatile("" ::: "memory");
-}
-
-__device__ __forceinline__ uint32_t lds_addr(const void *p) {
-  return static_cast<uint32_t>(reinterpret_cast<uintptr_t>(p));
-}
-
-// may be unaligned: gfx950 LDS serves unaligned dword reads
-__device__ __forceinline__ uint32_t lds_u32(uint32_t a) {
-  return *reinterpret_cast<const __attribute__((address_space(3))) uint32_t *>(static_cast<uintptr_t>(a));
-}
-
-__device__ __forceinline__ uint4 lds_u128(uint32_t a) {
-  const u32x4 x = *reinterpret_cast<const __attribute__((address_space(3))) u32x4 *>(static_cast<uintptr_t>(a));
-  return make_uint4(x.x, x.y, x.z, x.w);
-}
-
-__device__ __forceinline__ void lds_store_u128(uint32_t a, uint4 v) {
-  u32x4 x = {v.x, v.y, v.z, v.w};
-  *reinterpret_cast<__attribute__((address_space(3))) u32x4 *>(static_cast<uintptr_t>(a)) = x;
-}
-
-__device__ __forceinline__ void lds_store_u8(uint32_t a, uint8_t v) {
-  *reinterpret_cast<lds_u8 *>(static_cast<uintptr_t>(a)) = v;
-}
-
-__device__ __forceinline__ void lds_store_i32(uint32_t a, int32_t v) {
-  *reinterpret_cast<__attribute__((address_space(3))) int32_t *>(static_cast<uintptr_t>(a)) = v;
-}
-
-__device__ __forceinline__ void lds_store_u32(uint32_t a, uint32_t v) {
-  *reinterpret_cast<__attribute__((address_space(3))) uint32_t *>(static_cast<uintptr_t>(a)) = v;
-}
-
-__device__ __forceinline__ int32_t lds_i32(uint32_t a) {
-  return *reinterpret_cast<const __attribute__((address_space(3))) int32_t *>(static_cast<uintptr_t>(a));
-}
-
-#ifdef XSKNF_GUARD
-// Debug instrument (`make guard`, tools/guard_run.py): every UMEM access of the
-// split kernel's paths is checked against the ranges the host put in
-// g_guard[1..6] (umem, descriptors, verdicts); an access outside them is
-// recorded (source line, thread, address) and skipped -- a load reads the
-// descriptor array's first 16 bytes instead -- so a bad address is found
-// without faulting the GPU.  Not in the product library.
-__device__ unsigned long long *g_guard;
-template <typename P>
-__device__ __forceinline__ bool guard_ok(P p, uint32_t bytes, int site) {
-  unsigned long long *g = g_guard;
-  if (!g) return true;
-  const unsigned long long x = reinterpret_cast<uintptr_t>(p);
-  const bool ok = (x >= g[1] && x + bytes <= g[2]) || (x >= g[3] && x + bytes <= g[4]) ||
-                  (x >= g[5] && x + bytes <= g[6]);
-  if (!ok) {
-    const unsigned long long i = atomicAdd(g, 1ull);
-    if (i < 2048) {
-      g[8 + 2 * i] = (static_cast<unsigned long long>(site) << 32) | (blockIdx.x * 256u + threadIdx.x);
-      g[9 + 2 * i] = x;
-    }
-  }
-  return ok;
-}
-template <typename P>
-__device__ __forceinline__ P guard_ld(P p, uint32_t bytes, int site) {
-  return guard_ok(p, bytes, site) ? p : reinterpret_cast<P>(static_cast<uintptr_t>(g_guard[3]));
-}
-#define XSKNF_SITE , int site = __builtin_LINE()
-#define XSKNF_GLD(p, bytes) guard_ld(p, bytes, __LINE__)
-#define XSKNF_GST(p, bytes) if (guard_ok(p, bytes, __LINE__))
-#else
-#define XSKNF_SITE
-#define XSKNF_GLD(p, bytes) (p)
-#define XSKNF_GST(p, bytes)
-#endif
-
-// non-temporal 16-byte global load (streamed once)
-__device__ __forceinline__ uint4 load_nt(const uint4 *p XSKNF_SITE) {
-#ifdef XSKNF_GUARD
-  p = guard_ld(p, 16, site);
-#endif
-  const u32x4 x = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(p));
-  return make_uint4(x.x, x.y, x.z, x.w);
-}
-
-__device__ __forceinline__ void store_nt16(uint8_t *p, uint4 v XSKNF_SITE) {
-#ifdef XSKNF_GUARD
-  if (!guard_ok(p, 16, site)) return;
-#endif
-  u32x4 x = {v.x, v.y, v.z, v.w};
-  __builtin_nontemporal_store(x, reinterpret_cast<u32x4 *>(p));
-}
-
-// v with byte i (0..15) replaced by b; i outside 0..15 leaves v unchanged
-__device__ __forceinline__ uint4 put_byte(uint4 v, int i, uint32_t b) {
-  const uint32_t sh = 8u * (i & 3);
-  const uint32_t keep = ~(0xffu << sh), put = (b & 0xffu) << sh;
-  const int w = i >> 2;
-  if (i >= 0 && i < 16) {
-    v.x = w == 0 ? ((v.x & keep) | put) : v.x;
-    v.y = w == 1 ? ((v.y & keep) | put) : v.y;
-    v.z = w == 2 ? ((v.z & keep) | put) : v.z;
-    v.w = w == 3 ? ((v.w & keep) | put) : v.w;
-  }
-  return v;
-}
-
-// 0x01 in every byte b of the dword at window offset x with lo <= x+b < hi
-// (bytes [a, b) of a dword, a/b clamped to 0..4: two 64-bit shifts of 0x01010101).
-__device__ __forceinline__ uint32_t byte_ones(int lo, int hi, int x) {
-  const int a8 = min(max(8 * (lo - x), 0), 32);
-  const int b8 = min(max(8 * (hi - x), 0), 32);
-  const uint32_t below_b = static_cast<uint32_t>((0x01010101ull << b8) >> 32);
-  const uint32_t from_a = static_cast<uint32_t>(0x01010101ull << a8);
-  return below_b & from_a;
-}
-
-// Bytes of one 16-byte chunk inside [lo, hi) (window offsets), summed by weight
-// class: wl = bytes low in their 16-bit word, wh = high.
-__device__ __forceinline__ void chunk_sum(const uint4 v, int x, int lo, int hi, uint32_t wl,
-                                          uint32_t wh, uint32_t &acc_lo, uint32_t &acc_hi) {
-  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const uint32_t m = byte_ones(lo, hi, x + 4 * j);
-    acc_lo = __builtin_amdgcn_udot4(w[j], m & wl, acc_lo, false);
-    acc_hi = __builtin_amdgcn_udot4(w[j], m & wh, acc_hi, false);
-  }
-}
-
-// chunk_sum with a wave-uniform fast path: a chunk entirely inside or outside
-// [lo, hi) needs no byte mask, only an include predicate on the weights.  Only
-// when some lane of the wave holds a frame's head or tail chunk (at most two
-// chunk slots per frame) does the wave run the per-byte masks.
-__device__ __forceinline__ void chunk_sum_fast(const uint4 v, int x, int lo, int hi, uint32_t wl,
-                                               uint32_t wh, uint32_t &acc_lo, uint32_t &acc_hi) {
-  const bool inside = x >= lo && x + 16 <= hi;
-  const bool outside = x + 16 <= lo || x >= hi;
-  if (__builtin_amdgcn_ballot_w64(!inside && !outside)) {
-    chunk_sum(v, x, lo, hi, wl, wh, acc_lo, acc_hi);
-  } else {
-    const uint32_t l = inside ? wl : 0u, h = inside ? wh : 0u;
-    acc_lo = __builtin_amdgcn_udot4(v.x, l, acc_lo, false);
-    acc_hi = __builtin_amdgcn_udot4(v.x, h, acc_hi, false);
-    acc_lo = __builtin_amdgcn_udot4(v.y, l, acc_lo, false);
-    acc_hi = __builtin_amdgcn_udot4(v.y, h, acc_hi, false);
-    acc_lo = __builtin_amdgcn_udot4(v.z, l, acc_lo, false);
-    acc_hi = __builtin_amdgcn_udot4(v.z, h, acc_hi, false);
-    acc_lo = __builtin_amdgcn_udot4(v.w, l, acc_lo, false);
-    acc_hi = __builtin_amdgcn_udot4(v.w, h, acc_hi, false);
-  }
-}
-
-// Group sum via DPP (all lanes active): the total lands in the group's LAST lane.
-template <int LPF>
-__device__ __forceinline__ uint32_t group_sum_last(uint32_t v) {
-  v += __builtin_amdgcn_update_dpp(0u, v, 0x111, 0xf, 0xf, true);   // row_shr:1
-  v += __builtin_amdgcn_update_dpp(0u, v, 0x112, 0xf, 0xf, true);   // row_shr:2
-  if constexpr (LPF >= 8) v += __builtin_amdgcn_update_dpp(0u, v, 0x114, 0xf, 0xf, true);   // row_shr:4
-  if constexpr (LPF >= 16) v += __builtin_amdgcn_update_dpp(0u, v, 0x118, 0xf, 0xf, true);  // row_shr:8
-  if constexpr (LPF >= 32) v += __builtin_amdgcn_update_dpp(0u, v, 0x142, 0xa, 0xf, false); // row_bcast:15
-  if constexpr (LPF >= 64) v += __builtin_amdgcn_update_dpp(0u, v, 0x143, 0xc, 0xf, false); // row_bcast:31
-  return v;
-}
-
-__device__ __forceinline__ int lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-
-// The group's last lane's value on every lane of the group.
-template <int LPF>
-__device__ __forceinline__ uint32_t group_bcast_last(uint32_t v, int lane) {
-  return static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute((lane | (LPF - 1)) << 2, static_cast<int>(v)));
-}
-
-// ---- kernel arguments, frame references, descriptors -----------------------
-
-// struct KernelArgs: checksummer_internal.h
-
-// Check record parked in verdicts[f] by the summing pass (two-phase stores):
-// tag 01 in bits 31..30 (no verdict, -1 or 0..XSKNF_MAX_INTERFACES-1, has it),
-// u in bits 22..16, the new check in bits 15..0.
-// kRecTag / kRecTagMask: checksummer_internal.h
-
-// Where a frame's bytes are and which 16-byte chunks cover them.  Frames that
-// need no bytes (len < 14, or a descriptor outside the UMEM) point at a dummy
-// 16-byte block so that every chunk load can be unconditional.
-struct FrameRef {
-  const uint4 *cp;   // 16-byte aligned window start (cp <= fp)
-  uint8_t *fp;       // first byte of the frame
-  int rs;            // fp - cp, 0..15
-  int len;
-  int nch;           // chunks in the window, >= 1
-  bool exists;       // index < n
-  bool live;         // exists, in range and len >= 14
-};
-
-__device__ __forceinline__ FrameRef make_ref(const KernelArgs &a, uint64_t addr, uint32_t len, bool exists) {
-  FrameRef r;
-  const uint64_t off = umem_offset(addr);
-  // (frames of 2 GiB and more are treated as out of range: lengths are ints here)
-  const bool in_range = off <= a.umem_size && len <= a.umem_size - off && len < 0x80000000u;
-  r.exists = exists;
-  r.live = exists && in_range && len >= 14;
-  r.len = static_cast<int>(len);
-  if (r.live) {
-    r.fp = a.umem + off;
-    r.rs = static_cast<int>(reinterpret_cast<uintptr_t>(r.fp) & 15);
-    r.cp = reinterpret_cast<const uint4 *>(r.fp - r.rs);
-    r.nch = (r.rs + r.len + 15) >> 4;
-  } else {
-    r.fp = a.umem;
-    r.rs = 0;
-    r.cp = a.dummy;
-    r.nch = 1;
-  }
-  return r;
-}
-
-// Descriptors travel per tile: the 64 descriptors of a tile (1 KiB, contiguous)
-// are staged in LDS once, and each group reads its frame's descriptor there.
-__device__ __forceinline__ FrameRef ref_from_lds(const KernelArgs &a, uint32_t dslot, uint32_t f) {
-  const uint4 d = lds_u128(dslot);          // {addr lo, addr hi, len, options}
-  return make_ref(a, (static_cast<uint64_t>(d.y) << 32) | d.x, d.z, f < a.n);
-}
-
-// ---- per-frame parse / verdict / check (shared by both kernel families) -----
-
-struct Header {
-  int u;              // udp header offset 14 + 4*ihl (ihl unvalidated, :52)
-  bool ipv4, udp;
-  uint32_t pseudo;    // :57-65, read before the check is cleared
-  uint32_t old_check; // f[u+6..u+7], counted as 0 (:68)
-};
-
-// Frame byte i is at LDS address hb + i (hb may be unaligned).
-__device__ __forceinline__ Header parse_header(uint32_t hb) {
-  Header h;
-  const uint32_t w12 = lds_u32(hb + 12);   // f[12..15]
-  const uint32_t w20 = lds_u32(hb + 20);   // f[20..23]
-  const uint32_t w24 = lds_u32(hb + 24);   // f[24..27]
-  const uint32_t w28 = lds_u32(hb + 28);   // f[28..31]
-  const uint32_t w32 = lds_u32(hb + 32);   // f[32..35]
-  h.u = 14 + 4 * ((w12 >> 16) & 0x0f);
-  const uint32_t wu = lds_u32(hb + h.u + 4);  // f[u+4..u+7]
-  h.ipv4 = (w12 & 0xffffu) == 0x0008u;        // f[12..13] == 08 00
-  h.udp = (w20 >> 24) == 17u;                 // f[23]
-  // le16(26) + le16(28) + le16(30) + le16(32) + 17<<8 + le16(u+4)
-  h.pseudo = (w24 >> 16) + (w28 & 0xffffu) + (w28 >> 16) + (w32 & 0xffffu) + 0x1100u + (wu & 0xffffu);
-  h.old_check = wu >> 16;
-  return h;
-}
-
-// checksummer_user.c:34-55 and :110-111
-__device__ __forceinline__ int32_t verdict_of(const FrameRef &r, const Header &h, int32_t fwd, bool &do_sum) {
-  do_sum = false;
-  if (!r.live) return -1;                 // :34-37 (and out-of-range descriptors)
-  if (!h.ipv4) return 0;                  // :39-41
-  if (r.len < 34) return -1;              // :43-46
-  if (!h.udp) return 0;                   // :48-50
-  if (h.u + 8 > r.len) return -1;         // :53-55
-  do_sum = true;
-  return fwd;                             // :110-111
-}
-
-// :92-108 given the reduced payload sum P (old check still included)
-__device__ __forceinline__ uint16_t check_of(const Header &h, uint32_t P, uint32_t mult) {
-  const uint32_t s = h.pseudo + mult * (P - h.old_check);
-  return static_cast<uint16_t>(~static_cast<uint16_t>((s & 0xffffu) + (s >> 16)));
-}
-
-// Whether the new check c must be written.  :68 clears the check and :108
-// stores c: when c is the value the frame already holds (a NIC filled in the
-// UDP checksum, tests/gen-traffic.lua:120 -- the reference's own traffic), the
-// frame ends with the bytes it began with, and neither its sector nor a record
-// is written.  (old_check is the same 2 bytes read as a little-endian u16.)
-__device__ __forceinline__ bool check_changes(const KernelArgs &a, const Header &h, uint16_t c) {
-  return c != static_cast<uint16_t>(h.old_check) || a.store_unchanged;
-}
-
-// The word this frame leaves in verdicts[f] after the summing pass; the check
-// bytes are written here only in single-pass (fused) mode.
-__device__ __forceinline__ int32_t frame_result(const KernelArgs &a, const FrameRef &r, const Header &h,
-                                                int32_t verdict, bool do_sum, uint32_t P,
-                                                bool sector_done = false) {
-  if (!do_sum) return verdict;
-  const uint16_t c = check_of(h, P, a.payload_mult);
-  if (!check_changes(a, h, c)) return verdict;
-  if (static_cast<uint32_t>(r.len) >= a.defer_min_len)
-    return static_cast<int32_t>(kRecTag | (static_cast<uint32_t>(h.u) << 16) | c);
-  if (!sector_done) *reinterpret_cast<uint16_t *>(r.fp + h.u + 6) = c;   // :108
-  return verdict;
-}
-
-// In-line check as a whole-sector rewrite (register kernel, pass-0 frames):
-// when the check's 64-byte sector lies inside the frame, the (up to 4) lanes
-// whose 16-byte chunks make up that sector patch the check bytes into the
-// chunk they loaded and store it back non-temporally -- one full-sector write
-// instead of a 2-byte partial write, which HBM turns into read-modify-write.
-// Returns true (on every lane of the group) when the sector was written.
-template <int LPF, int NCH>
-__device__ __forceinline__ bool store_check_sector(const FrameRef &r, const Header &h, uint16_t c,
-                                                   const uint4 (&v)[NCH], int gl) {
-  const uintptr_t f0 = reinterpret_cast<uintptr_t>(r.fp);
-  const uintptr_t ck = f0 + h.u + 6;
-  const uintptr_t sec = ck & ~static_cast<uintptr_t>(63);
-  if (sec < f0 || sec + 64 > f0 + r.len || (ck & 63) == 63) return false;
-  const uintptr_t c0 = reinterpret_cast<uintptr_t>(r.cp);
-#pragma unroll
-  for (int k = 0; k < NCH; ++k) {
-    const uintptr_t piece = c0 + 16u * static_cast<uint32_t>(k * LPF + gl);
-    if (piece >= sec && piece < sec + 64) {
-      const int o = static_cast<int>(static_cast<intptr_t>(ck - piece));
-      uint4 w = put_byte(v[k], o, c);
-      w = put_byte(w, o + 1, c >> 8);
-      store_nt16(r.fp + static_cast<intptr_t>(piece - f0), w);   // global addressing from fp
-    }
-  }
-  return true;
-}
-
-// Frames longer than one pass.  The pipelined step only sums pass 0 and parks
-// the frame as PENDING (tag 10 in bits 31..30 of its result word, u below, the
-// partial sum pseudo + mult*(P0 - old_check) in part[i]); the remaining passes
-// run at the end of the tile, when no prefetch buffer is live (keeping them in
-// the step would cost ~60 VGPRs of occupancy for a rare case).
-constexpr uint32_t kPendTag = 0x80000000u;
-// kNoDefer (defer_min_len: every check in-line): checksummer_internal.h
-constexpr uint32_t kDeferTileK = 2;   // a tile defers when K * (long frames) >= live frames
-constexpr uint32_t kDeferMinLen = 1024;        // hybrid default (tools/tune.py: 64 B, 570 B
-                                               // and IMIX prefer in-line, 1500 B deferred)
-
-// Result word of a frame after its pass-0 sum P0 (group-reduced, last lane).
-__device__ __forceinline__ int32_t step_result(const KernelArgs &a, const FrameRef &r, const Header &h,
-                                               int32_t verdict, bool do_sum, uint32_t P0, int span,
-                                               uint32_t part_addr, bool sector_done = false) {
-  if (do_sum && r.nch > span) {
-    lds_store_u32(part_addr, h.pseudo + a.payload_mult * (P0 - h.old_check));
-    return static_cast<int32_t>(kPendTag | static_cast<uint32_t>(h.u));
-  }
-  return frame_result(a, r, h, verdict, do_sum, P0, sector_done);
-}
-
-// Finish the PENDING frames of a tile: passes 1.. of each, then their result.
-// dsc: the tile's descriptors in LDS; rec / part: the tile's result words and
-// partial sums in LDS (index step * G + group).
-template <int LPF, int NCH>
-__device__ __forceinline__ void finish_long_frames(const KernelArgs &a, uint32_t dsc, uint32_t tf0, uint32_t rec,
-                                                uint32_t part, int steps, int grp, int gl) {
-  constexpr int G = kWave / LPF;
-  constexpr int SPAN = LPF * NCH;
-  for (int st = 0; st < steps; ++st) {
-    const uint32_t i = st * G + grp;
-    const uint32_t rv = static_cast<uint32_t>(lds_i32(rec + 4 * i));
-    const bool pend = (rv & kRecTagMask) == kPendTag && tf0 + i < a.n;
-    if (!__builtin_amdgcn_ballot_w64(pend)) continue;
-    const FrameRef r = ref_from_lds(a, dsc + 16 * i, tf0 + i);
-    const int u = static_cast<int>(rv & 0x7f);
-    const int lo = r.rs + u, hi = pend ? r.rs + r.len : lo;   // idle groups sum nothing
-    const uint32_t wl = (lo & 1) ? 0x01000100u : 0x00010001u;
-    const uint32_t wh = wl << 8 | wl >> 24;
-    uint32_t acc_lo = 0, acc_hi = 0;
-    for (int p = SPAN; __builtin_amdgcn_ballot_w64(pend && p < r.nch); p += SPAN) {
-      uint4 t[NCH];
-#pragma unroll
-      for (int k = 0; k < NCH; ++k) t[k] = load_nt(r.cp + min(p + k * LPF + gl, r.nch - 1));
-#pragma unroll
-      for (int k = 0; k < NCH; ++k) chunk_sum_fast(t[k], (p + k * LPF + gl) * 16, lo, hi, wl, wh, acc_lo, acc_hi);
-    }
-    const uint32_t Prest = group_sum_last<LPF>(acc_lo + (acc_hi << 8));
-    if (gl == LPF - 1 && pend) {
-      const uint32_t sum = lds_i32(part + 4 * i) + a.payload_mult * Prest;   // :92-103
-      const uint16_t c = static_cast<uint16_t>(~static_cast<uint16_t>((sum & 0xffffu) + (sum >> 16)));
-      int32_t res = a.fwd_verdict;
-      // the old check, for check_changes (pass 0's window is gone: 2 bytes from the frame)
-      const uint16_t old = static_cast<uint16_t>(r.fp[u + 6] | (r.fp[u + 7] << 8));
-      if (c == old && !a.store_unchanged) {
-        // the frame already holds c: nothing to write
-      } else if (static_cast<uint32_t>(r.len) >= a.defer_min_len)
-        res = static_cast<int32_t>(kRecTag | (static_cast<uint32_t>(u) << 16) | c);
-      else *reinterpret_cast<uint16_t *>(r.fp + u + 6) = c;   // :108
-      lds_store_i32(rec + 4 * i, res);
-    }
-  }
-}
-
-// Records per launch, for the scatter pass to pick its shape and to skip
-// itself when nothing was parked (per device: a __device__ variable exists once
-// per GPU).  Launch `seq` publishes into set seq % kCountSlots, 64 counter words
-// on separate 64-byte lines (block b adds to word b % 64: one shared address
-// would serialize the publishing atomics in one L2 channel).  A word is
-// {launch seq (high 32 bits), records (low 32)}: a wave adds to it while it
-// carries its own seq and restarts it (CAS) while it carries an older one.  The
-// scatter pass sums the words tagged with its seq; words tagged older are a
-// zero of this launch; a word tagged NEWER means a launch kCountSlots later
-// reused the set while this one was in flight, and the count is unknown (the
-// pass then scans every frame).  So "no records" is exact when it is reported.
-constexpr uint32_t kCountSlots = 64;
-constexpr uint32_t kCountLanes = 64;
-constexpr uint32_t kCountStride = 8;           // u64 words = 64 bytes
-constexpr uint32_t kCountUnknown = 0xffffffffu;
-__device__ unsigned long long g_rec_count[kCountSlots][kCountLanes][kCountStride];
-
-// Store a tile's result word (lane's frame); returns the tile's record count
-// (wave-uniform), which the wave adds up and publishes once, at exit: an
-// atomic per tile would hold every following vmcnt wait on its L2 round trip.
-__device__ __forceinline__ uint32_t store_result(const KernelArgs &a, uint32_t f, bool valid, int32_t v) {
-  if (valid) {
-    XSKNF_GST(a.verdicts + f, 4) a.verdicts[f] = v;
-  }
-  if (!a.count_records) return 0;
-  return static_cast<uint32_t>(__builtin_popcountll(
-      __builtin_amdgcn_ballot_w64(valid && (static_cast<uint32_t>(v) & kRecTagMask) == kRecTag)));
-}
-
-__device__ __forceinline__ void publish_records(const KernelArgs &a, uint32_t nrec, int lane) {
-  if (!a.count_records || lane != 0 || !nrec) return;
-  unsigned long long *w = &g_rec_count[a.seq % kCountSlots][blockIdx.x % kCountLanes][0];
-  unsigned long long old = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  for (;;) {
-    const uint32_t tag = static_cast<uint32_t>(old >> 32);
-    if (tag == a.seq) { atomicAdd(w, static_cast<unsigned long long>(nrec)); return; }
-    if (static_cast<int32_t>(tag - a.seq) > 0) return;   // a newer launch owns the word
-    const unsigned long long mine = (static_cast<unsigned long long>(a.seq) << 32) | nrec;
-    const unsigned long long prev = atomicCAS(w, old, mine);
-    if (prev == old) return;
-    old = prev;
-  }
-}
-
-// The launch's record count on every lane (kCountUnknown if the set was reused).
-__device__ __forceinline__ uint32_t launch_records(const KernelArgs &a) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const unsigned long long w = __hip_atomic_load(&g_rec_count[a.seq % kCountSlots][lane % kCountLanes][0],
-                                                 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const uint32_t tag = static_cast<uint32_t>(w >> 32);
-  uint32_t c = tag == a.seq ? static_cast<uint32_t>(w) : 0u;
-  const bool newer = tag != a.seq && static_cast<int32_t>(tag - a.seq) > 0;
-  if (__builtin_amdgcn_ballot_w64(newer)) return kCountUnknown;
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) c += static_cast<uint32_t>(__shfl_xor(static_cast<int>(c), o, kWave));
-  return c;
-}
-
-// Write a finished tile's results (LDS rec[0..63]) as one coalesced store.
-__device__ __forceinline__ uint32_t flush_tile(const KernelArgs &a, uint32_t rec, uint32_t tile_f0, int lane) {
-  compiler_barrier();
-  const int32_t v = lds_i32(rec + 4 * lane);
-  const uint32_t nrec = store_result(a, tile_f0 + lane, tile_f0 + lane < a.n, v);
-  compiler_barrier();
-  return nrec;
-}
-
-// ---- register kernel ----------------------------------------------------------
-//
-// A wave works through tiles of SPT steps x G frames (consecutive frames; the
-// grid strides over tiles).  Inside a tile the step loop is fully unrolled over
-// two register buffers: the loads of step s+1 are issued before step s is
-// parsed / summed / reduced, and because the code is straight-line the compiler
-// counts vmcnt exactly (a loop-carried load would make it drain to 0).
-
-template <int LPF, int NCH>
-__device__ __forceinline__ void load_frame(const FrameRef &r, int gl, uint4 (&v)[NCH]) {
-#pragma unroll
-  for (int k = 0; k < NCH; ++k) v[k] = load_nt(r.cp + min(k * LPF + gl, r.nch - 1));
-}
-
-template <int LPF, int NCH>
-__device__ __forceinline__ int32_t process_regs(const KernelArgs &args, const FrameRef &r, const uint4 (&v)[NCH],
-                                                uint32_t slot, int gl, uint32_t part_addr) {
-  // header window (chunks 0..6) to LDS; one wave's LDS accesses execute in issue
-  // order, only the compiler must not move the reads above the writes
-#pragma unroll
-  for (int k = 0; k < NCH; ++k) {
-    const int c = k * LPF + gl;
-    if (k * LPF < kHdrChunks && c < kHdrChunks) lds_store_u128(slot + 16 * c, v[k]);
-  }
-  compiler_barrier();
-  const Header h = parse_header(slot + r.rs);
-  compiler_barrier();
-  bool do_sum;
-  const int32_t verdict = verdict_of(r, h, args.fwd_verdict, do_sum);
-  const int lo = r.rs + h.u, hi = r.rs + r.len;
-  const uint32_t wl = (lo & 1) ? 0x01000100u : 0x00010001u;
-  const uint32_t wh = wl << 8 | wl >> 24;
-  uint32_t acc_lo = 0, acc_hi = 0;
-#pragma unroll
-  for (int k = 0; k < NCH; ++k) chunk_sum_fast(v[k], (k * LPF + gl) * 16, lo, hi, wl, wh, acc_lo, acc_hi);
-  const uint32_t P0 = group_sum_last<LPF>(acc_lo + (acc_hi << 8));
-  bool sector_done = false;
-  if (args.sector_stores && __builtin_amdgcn_ballot_w64(do_sum && r.nch <= LPF * NCH &&
-                                                        static_cast<uint32_t>(r.len) < args.defer_min_len)) {
-    const uint32_t P = group_bcast_last<LPF>(P0, lane_id());
-    const uint16_t c = check_of(h, P, args.payload_mult);
-    if (do_sum && r.nch <= LPF * NCH && static_cast<uint32_t>(r.len) < args.defer_min_len &&
-        check_changes(args, h, c))
-      sector_done = store_check_sector<LPF, NCH>(r, h, c, v, gl);
-  }
-  return (gl == LPF - 1 && r.exists)
-             ? step_result(args, r, h, verdict, do_sum, P0, LPF * NCH, part_addr, sector_done) : 0;
-}
-
-// The register kernel's tiles of block `blk` of `nblk` (a launch's blockIdx /
-// gridDim, or the resident worker's blocks over one ring batch).
-template <int LPF, int NCH, int SPT>
-__device__ __forceinline__ void group_tiles(const KernelArgs &args, uint32_t blk, uint32_t nblk) {
-  static_assert(kWave % LPF == 0 && LPF >= 4, "LPF must divide the wave");
-  static_assert(LPF * NCH >= kHdrChunks, "pass 0 must cover the header window");
-  constexpr int G = kWave / LPF;
-  constexpr int T = SPT * G;                 // frames per tile
-  static_assert(T <= kWave, "one descriptor / result per lane");
-
-  __shared__ __attribute__((aligned(16))) uint8_t hdr[kWavesPerBlock][G][kSlotBytes];
-  __shared__ __attribute__((aligned(16))) int32_t recs[kWavesPerBlock][kWave];
-  __shared__ __attribute__((aligned(16))) uint32_t parts[kWavesPerBlock][kWave];
-  __shared__ __attribute__((aligned(16))) xsknf_gpu_desc dtile[kWavesPerBlock][kWave];
-
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-  const int grp = lane / LPF;
-  const int gl = lane % LPF;
-  const uint32_t slot = lds_addr(&hdr[wv][grp][0]);
-  const uint32_t rec = lds_addr(&recs[wv][0]);
-  const uint32_t part = lds_addr(&parts[wv][0]);
-  const uint32_t dsc = lds_addr(&dtile[wv][0]);
-  const uint32_t waves = nblk * kWavesPerBlock;
-  const uint32_t last = args.n - 1;
-
-  // the next tile's descriptors ride in VGPRs (lane l: frame l of the tile)
-  uint32_t tile = blk * kWavesPerBlock + wv;
-  uint32_t nrec = 0;                         // records this wave parked (wave-uniform)
-  uint4 dnext = *reinterpret_cast<const uint4 *>(args.descs + min(tile * T + min(lane, T - 1), last));
-  for (; tile * T < args.n; tile += waves) {
-    const uint32_t tf0 = tile * T;
-    compiler_barrier();
-    if (lane < T) lds_store_u128(dsc + 16 * lane, dnext);
-    compiler_barrier();
-    // per-tile store policy: long frames defer their checks only where they are
-    // at least half of the tile (a 1500 B batch); in a mix (IMIX: 1 in 12) they
-    // write in-line, which is cheaper than a scatter pass for a few frames
-    KernelArgs ta = args;
-    if (args.defer_min_len != kNoDefer && args.defer_min_len != 0 && !args.no_scatter) {
-      const uint32_t nlong = static_cast<uint32_t>(__builtin_popcountll(
-          __builtin_amdgcn_ballot_w64(lane < T && tf0 + lane < args.n && dnext.z >= args.defer_min_len)));
-      const uint32_t nlive = min(static_cast<uint32_t>(T), args.n - tf0);
-      if (kDeferTileK * nlong < nlive) ta.defer_min_len = kNoDefer;
-    }
-    dnext = *reinterpret_cast<const uint4 *>(args.descs + min((tile + waves) * T + min(lane, T - 1), last));
-
-    uint4 va[NCH], vb[NCH];
-    FrameRef ra = ref_from_lds(args, dsc + 16 * grp, tf0 + grp), rb;
-    load_frame<LPF, NCH>(ra, gl, va);
-#pragma unroll
-    for (int st = 0; st < SPT; ++st) {
-      // even steps: process (ra, va), prefetch into (rb, vb); odd steps: swapped
-      FrameRef &rc = (st & 1) ? rb : ra;
-      FrameRef &rn = (st & 1) ? ra : rb;
-      uint4 (&vc)[NCH] = (st & 1) ? vb : va;
-      uint4 (&vn)[NCH] = (st & 1) ? va : vb;
-      if (st + 1 < SPT) {
-        const uint32_t i = (st + 1) * G + grp;
-        rn = ref_from_lds(args, dsc + 16 * i, tf0 + i);
-        load_frame<LPF, NCH>(rn, gl, vn);
-      }
-      const int32_t res = process_regs<LPF, NCH>(ta, rc, vc, slot, gl, part + 4 * (st * G + grp));
-      if (gl == LPF - 1 && rc.exists) lds_store_i32(rec + 4 * (st * G + grp), res);
-      compiler_barrier();   // the next frame rewrites this group's header window
-    }
-    compiler_barrier();
-    finish_long_frames<LPF, NCH>(ta, dsc, tf0, rec, part, SPT, grp, gl);
-    compiler_barrier();
-    nrec += store_result(args, tf0 + lane, lane < T && tf0 + lane < args.n, lds_i32(rec + 4 * min(lane, T - 1)));
-    compiler_barrier();
-  }
-  publish_records(args, nrec, lane);
-}
-
-template <int LPF, int NCH, int SPT>
-__global__ __launch_bounds__(kBlock) void checksum_kernel(const KernelArgs args) {
-  group_tiles<LPF, NCH, SPT>(args, blockIdx.x, gridDim.x);
-}
-
-// ---- lane-per-frame kernel (small frames) ---------------------------------------
-//
-// One lane owns a whole frame: it loads the frame's first NCH 16-byte chunks
-// itself, parses the header from its own LDS slot, sums with no cross-lane
-// reduction and writes its check from its own registers.  For 64 B frames the
-// group kernels spend most of their time on per-frame overhead (descriptor,
-// header, reduction for 8 frames per wave step); here a wave step covers 64
-// frames.  A wave works through tiles of SPT steps (64 * SPT consecutive frames)
-// with the two-buffer unrolled pipeline of the register kernel; the tile's
-// descriptors ride in registers, loaded one tile ahead.  Chunks past NCH (frames
-// longer than the window) are loaded and summed in a per-lane tail loop.
-
-constexpr int kLaneSlot = 16 * kHdrChunks;   // per-lane LDS header window
-
-// Default-policy loads: a lane's chunks of one frame arrive in NCH separate
-// (uncoalesced) instructions, and the line must stay in L2 between them (and
-// for the sector store that follows); non-temporal loads refetch it.
-// Chunks 4 and up are loaded only when some frame of the wave's step reaches
-// them (a wave-uniform branch): a step of 16-byte-aligned 64 B frames then
-// issues 4 load instructions of a 5-chunk window, not 5 (the fifth re-read
-// the fourth chunk: one more instruction's worth of requests per frame), and a
-// step with frames at odd starts still loads its 5 chunks at once.
-template <int NCH>
-__device__ __forceinline__ void load_lane(const FrameRef &r, uint4 (&v)[NCH]) {
-#pragma unroll
-  for (int k = 0; k < NCH; ++k) {
-    if (k < 4 || __builtin_amdgcn_ballot_w64(k < r.nch))
-      v[k] = *XSKNF_GLD(r.cp + min(k, r.nch - 1), 16);
-    else
-      v[k] = make_uint4(0, 0, 0, 0);   // past every frame of the step: outside every sum and parse
-  }
-}
-
-// Transposed window load (the lane kernel's TL shapes): the NCH chunks of the
-// step's 64 frames as NCH instructions whose lanes walk the frames' windows in
-// order -- lanes NCH*i .. NCH*i+NCH-1 read frame i's window, one coalesced
-// request per frame -- instead of NCH instructions that each send a 16-byte
-// request to every frame.  x[p] holds chunk (64 p + lane) % NCH of frame
-// (64 p + lane) / NCH; store_lane_tl drops it into that frame's LDS slot.
-template <int NCH>
-__device__ __forceinline__ void load_lane_tl(const FrameRef &r, uint4 (&x)[NCH]) {
-  const int lane = lane_id();
-  const uintptr_t cpv = reinterpret_cast<uintptr_t>(r.cp);
-#pragma unroll
-  for (int p = 0; p < NCH; ++p) {
-    const int j = kWave * p + lane;
-    const int f = j / NCH, c = j % NCH;
-    const uint32_t lo = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(f << 2, static_cast<int>(cpv)));
-    const uint32_t hi = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(f << 2, static_cast<int>(cpv >> 32)));
-    const int nc = __builtin_amdgcn_ds_bpermute(f << 2, r.nch);
-    const uint4 *cp = reinterpret_cast<const uint4 *>((static_cast<uintptr_t>(hi) << 32) | lo);
-    x[p] = *XSKNF_GLD(cp + min(c, nc - 1), 16);
-  }
-}
-
-template <int NCH>
-__device__ __forceinline__ void store_lane_tl(uint32_t area, const uint4 (&x)[NCH]) {
-  const int lane = lane_id();
-#pragma unroll
-  for (int p = 0; p < NCH; ++p) {
-    const int j = kWave * p + lane;
-    lds_store_u128(area + kLaneSlot * (j / NCH) + 16 * (j % NCH), x[p]);
-  }
-}
-
-#ifdef XSKNF_TIMELINE
-// A/B instrument (tools/timeline.py): per wave of the split and lane kernels, the
-// constant 100 MHz clock at its start, after its last tile, after its patches,
-// and its tile count, so the step can be split into stream and patch time.
-__device__ unsigned long long *g_timeline;
-// 8 u64 per wave: start, stream done, patches done, tiles, then the clock
-// summed over the wave's tiles in phase A (window loads until they are in
-// LDS), phase A's parse, and phase B (payload items)
-__device__ __forceinline__ void timeline_put(uint32_t wave, int lane, unsigned long long t0, unsigned long long t1,
-                                             int tiles, unsigned long long sa, unsigned long long sp,
-                                             unsigned long long sb) {
-  const unsigned long long t2 = wall_clock64();
-  unsigned long long *p = g_timeline;
-  const unsigned long long v[8] = {t0, t1, t2, static_cast<unsigned long long>(tiles), sa, sp, sb, 0ull};
-  unsigned long long x = 0;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) x = lane == k ? v[k] : x;
-  if (p && lane < 8) p[8ull * wave + lane] = x;
-}
-#endif
-
-// A lane's result; when `sector` is set, the frame's patched 64-byte check
-// sector sits in the lane's LDS slot at `lds_sec`, to be written to `gsec` by
-// the wave's cooperative store (store_sectors).
-struct LaneOut {
-  int32_t res;
-  bool sector;
-  uint32_t lds_sec;
-  uint8_t *gsec;
-};
-
-// kInSlot: the window is already in the lane's slot (transposed load), v holds a copy
-template <int NCH, bool kInSlot = false>
-__device__ __forceinline__ LaneOut process_lane(const KernelArgs &args, const FrameRef &r, const uint4 (&v)[NCH],
-                                                uint32_t slot) {
-  static_assert(NCH >= 4 && NCH <= kHdrChunks, "lane window");
-  LaneOut out = {0, false, slot, r.fp};
-  if constexpr (!kInSlot) {
-#pragma unroll
-    for (int k = 0; k < NCH; ++k) lds_store_u128(slot + 16 * k, v[k]);
-  }
-  const int need = min(kHdrChunks, r.nch);   // header bytes past the window (large ihl)
-  for (int k = NCH; k < need; ++k) lds_store_u128(slot + 16 * k, *XSKNF_GLD(r.cp + k, 16));
-  compiler_barrier();
-  const Header h = parse_header(slot + r.rs);
-  compiler_barrier();
-  bool do_sum;
-  const int32_t verdict = verdict_of(r, h, args.fwd_verdict, do_sum);
-  if (!r.exists) return out;
-  out.res = verdict;
-  if (!do_sum) return out;
-  const int lo = r.rs + h.u, hi = r.rs + r.len;
-  const uint32_t wl = (lo & 1) ? 0x01000100u : 0x00010001u;
-  const uint32_t wh = wl << 8 | wl >> 24;
-  uint32_t acc_lo = 0, acc_hi = 0;
-#pragma unroll
-  for (int k = 0; k < NCH; ++k) chunk_sum(v[k], 16 * k, lo, hi, wl, wh, acc_lo, acc_hi);
-  for (int k = NCH; k < r.nch; ++k) chunk_sum(*XSKNF_GLD(r.cp + k, 16), 16 * k, lo, hi, wl, wh, acc_lo, acc_hi);
-  const uint16_t c = check_of(h, acc_lo + (acc_hi << 8), args.payload_mult);
-  if (!check_changes(args, h, c)) return out;
-  if (static_cast<uint32_t>(r.len) >= args.defer_min_len) {
-    out.res = static_cast<int32_t>(kRecTag | (static_cast<uint32_t>(h.u) << 16) | c);
-    return out;
-  }
-  // in-line: the whole 64-byte sector when it lies inside the frame and the
-  // window (patched in the LDS copy, stored by the wave), else the 2 bytes
-  const uintptr_t f0 = reinterpret_cast<uintptr_t>(r.fp);
-  const uintptr_t ck = f0 + h.u + 6;
-  const uintptr_t sec = ck & ~static_cast<uintptr_t>(63);
-  const uintptr_t c0 = reinterpret_cast<uintptr_t>(r.cp);
-  if (args.sector_stores && sec >= f0 && sec + 64 <= f0 + r.len && (ck & 63) != 63 && sec >= c0 &&
-      sec + 64 <= c0 + 16 * NCH) {
-    const uint32_t at = slot + static_cast<uint32_t>(ck - c0);
-    lds_store_u8(at, static_cast<uint8_t>(c));
-    lds_store_u8(at + 1, static_cast<uint8_t>(c >> 8));
-    out.sector = true;
-    out.lds_sec = slot + static_cast<uint32_t>(sec - c0);
-    out.gsec = r.fp + static_cast<intptr_t>(sec - f0);   // global addressing from fp
-  } else {
-    XSKNF_GST(r.fp + h.u + 6, 2) *reinterpret_cast<uint16_t *>(r.fp + h.u + 6) = c;   // :108
-  }
-  return out;
-}
-
-// One 16-byte piece of an in-line check sector: non-temporal, or (wt) sc1 nt,
-// written through the XCD's L2 at once.  Frames 2 KiB apart (the aligned
-// UMEM) share no line, and there the write-through store leaves no dirty line
-// for the end of the launch to write back: 64 B 58.0-58.3 vs 60.1-60.5 us; for
-// frames packed back to back (-u) it costs 38.2 -> 42.2 us, sectors there
-// sharing their 128-byte lines (profiles/r05/ab/ab_lane_sc*.jsonl; sc1 alone
-// and sc0 sc1: no gain).
-__device__ __forceinline__ void store_sector16(uint8_t *p, uint4 v, bool wt XSKNF_SITE) {
-  if (!wt) {
-    store_nt16(p, v);
-    return;
-  }
-#ifdef XSKNF_GUARD
-  if (!guard_ok(p, 16, site)) return;
-#endif
-  const u32x4 x = {v.x, v.y, v.z, v.w};
-  // (s_nop 1: the store reads its data registers after issue, and the next
-  // instruction hipcc places after the statement may overwrite them)
-  asm volatile("global_store_dwordx4 %0, %1, off sc1 nt\n\ts_nop 1" ::"v"(p), "v"(x) : "memory");
-}
-
-// The wave's patched sectors, 16 per instruction: lanes 4i..4i+3 write the 4
-// pieces of lane (16p + i)'s sector -- one coalesced 64-byte request each,
-// instead of 4 separate 16-byte stores per lane.
-__device__ __forceinline__ void store_sectors(const LaneOut &o, int lane, bool plain, bool wt = false) {
-  const uint64_t any = __builtin_amdgcn_ballot_w64(o.sector);
-  if (!any) return;
-  compiler_barrier();
-  const uint32_t glo = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(o.gsec));
-  const uint32_t ghi = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(o.gsec) >> 32);
-#pragma unroll
-  for (int p = 0; p < kWave / 16; ++p) {
-    if (!((any >> (16 * p)) & 0xffffull)) continue;
-    const int src = 16 * p + (lane >> 2);
-    const int sa = src << 2;
-    const uint32_t lo = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(sa, static_cast<int>(glo)));
-    const uint32_t hi = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(sa, static_cast<int>(ghi)));
-    const uint32_t ls = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(sa, static_cast<int>(o.lds_sec)));
-    if ((any >> src) & 1) {
-      uint8_t *g = reinterpret_cast<uint8_t *>((static_cast<uintptr_t>(hi) << 32) | lo);
-      const uint4 w = lds_u128(ls + 16 * (lane & 3));
-      if (plain) {
-        XSKNF_GST(g + 16 * (lane & 3), 16) *reinterpret_cast<uint4 *>(g + 16 * (lane & 3)) = w;
-      } else {
-        store_sector16(g + 16 * (lane & 3), w, wt);
-      }
-    }
-  }
-  compiler_barrier();
-}
-
-__device__ __forceinline__ FrameRef lane_ref(const KernelArgs &a, const uint4 d, uint32_t f) {
-  return make_ref(a, (static_cast<uint64_t>(d.y) << 32) | d.x, d.z, f < a.n);
-}
-
-constexpr uint32_t kNoTile = 0xffffffffu;   // no tile / unit
-
-// SW > 4 (one 16-wave block per CU): the block's tiles, every nb-th from the
-// block index, are a pool its waves claim from through an LDS counter, one
-// tile ahead, as the split kernel's pool (a CU's waves do not stream equally
-// fast; from a shared pool the faster ones take more tiles).
-// TLM: 0 = every lane loads its own frame's window (load_lane), 1 = transposed
-// window loads (load_lane_tl), 2 = per tile: transposed when the tile's frames
-// lie apart (a 2 KiB-chunk UMEM, or frames in fill-ring order: one coalesced
-// request per frame instead of NCH), per lane when they are packed back to
-// back (the -u layout: the lanes' own loads already stream, and the transposed
-// path's LDS round trip costs more than it saves).
-template <int NCH, int SPT, int SW = kWavesPerBlock, int WPE = 1, int TLM = 0>
-__global__ __launch_bounds__(SW * kWave) __attribute__((amdgpu_waves_per_eu(WPE)))
-void checksum_kernel_lane(const KernelArgs args) {
-  constexpr uint32_t T = SPT * kWave;        // frames per tile
-  constexpr bool kPool = SW > kWavesPerBlock;
-  __shared__ __attribute__((aligned(16))) uint8_t hdr[SW][kWave][kLaneSlot];
-  __shared__ uint32_t pool_next;
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-  const uint32_t slot = lds_addr(&hdr[wv][lane][0]);
-  const uint32_t waves = gridDim.x * SW;
-  const uint32_t last = args.n - 1;
-  const uint32_t ntiles = (args.n + T - 1) / T, nb = gridDim.x;
-  const uint32_t bt = ntiles > blockIdx.x ? (ntiles - blockIdx.x + nb - 1) / nb : 0u;   // the block's tiles
-
-  uint32_t tile;
-  if constexpr (kPool) {
-    tile = static_cast<uint32_t>(wv) < bt ? blockIdx.x + wv * nb : kNoTile;
-    if (threadIdx.x == 0) pool_next = SW;
-    __syncthreads();
-  } else {
-    tile = blockIdx.x * SW + wv < ntiles ? blockIdx.x * SW + wv : kNoTile;
-  }
-  const auto desc_at = [&](uint32_t t, int st) {
-    return *XSKNF_GLD(reinterpret_cast<const uint4 *>(args.descs + (t == kNoTile ? last : min(t * T + st * kWave + lane, last))), 16);
-  };
-  uint32_t nrec = 0;
-#ifdef XSKNF_TIMELINE
-  const unsigned long long tl0 = wall_clock64();
-  int tl_tiles = 0;
-#endif
-  uint4 dn[SPT];
-#pragma unroll
-  for (int st = 0; st < SPT; ++st) dn[st] = desc_at(tile, st);
-  while (tile != kNoTile) {
-    const uint32_t tf0 = tile * T;
-#ifdef XSKNF_TIMELINE
-    ++tl_tiles;
-#endif
-    uint32_t next;
-    if constexpr (kPool) {
-      uint32_t dq = 0;
-      if (lane == 0) dq = __hip_atomic_fetch_add(&pool_next, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      const uint32_t p = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(dq), 0));
-      next = p < bt ? blockIdx.x + p * nb : kNoTile;
-    } else {
-      next = tile + waves < ntiles ? tile + waves : kNoTile;
-    }
-    uint4 d[SPT];
-#pragma unroll
-    for (int st = 0; st < SPT; ++st) {
-      d[st] = dn[st];
-      dn[st] = desc_at(next, st);
-    }
-    uint4 v[2][NCH];
-    FrameRef r[2];
-    r[0] = lane_ref(args, d[0], tf0 + lane);
-    bool tl = TLM == 1;
-    bool wt = false;   // in-line sectors written through (store_sector16)
-    {
-      // the tile's first and last frames' offsets: 64 frames packed back to back
-      // span a few KiB, 64 chunks of a 2 KiB-chunk UMEM 126 KiB
-      const uint64_t off = reinterpret_cast<uintptr_t>(r[0].fp) - reinterpret_cast<uintptr_t>(args.umem);
-      const uint64_t o0 = static_cast<uint64_t>(__builtin_amdgcn_readlane(static_cast<int>(off), 0)) |
-                          static_cast<uint64_t>(__builtin_amdgcn_readlane(static_cast<int>(off >> 32), 0)) << 32;
-      const uint64_t o1 = static_cast<uint64_t>(__builtin_amdgcn_readlane(static_cast<int>(off), kWave - 1)) |
-                          static_cast<uint64_t>(__builtin_amdgcn_readlane(static_cast<int>(off >> 32), kWave - 1)) << 32;
-      const bool apart = (o1 > o0 ? o1 - o0 : o0 - o1) >= static_cast<uint64_t>(kWave - 1) * 256;
-      if constexpr (TLM == 2) tl = apart;
-      wt = apart;
-    }
-    if (tl) load_lane_tl<NCH>(r[0], v[0]); else load_lane<NCH>(r[0], v[0]);
-#pragma unroll
-    for (int st = 0; st < SPT; ++st) {
-      // step st: process buffer st & 1, prefetch step st + 1 into the other
-      if (st + 1 < SPT) {
-        r[(st + 1) & 1] = lane_ref(args, d[st + 1], tf0 + (st + 1) * kWave + lane);
-        if (tl) load_lane_tl<NCH>(r[(st + 1) & 1], v[(st + 1) & 1]);
-        else load_lane<NCH>(r[(st + 1) & 1], v[(st + 1) & 1]);
-      }
-      LaneOut o;
-      if (tl) {
-        // the step's windows into their frames' slots (the previous step's
-        // reads of the slots are done: a wave's LDS operations stay in order),
-        // then each lane reads its own frame's back
-        compiler_barrier();
-        store_lane_tl<NCH>(lds_addr(&hdr[wv][0][0]), v[st & 1]);
-        compiler_barrier();
-        uint4 own[NCH];
-#pragma unroll
-        for (int k = 0; k < NCH; ++k) own[k] = lds_u128(slot + 16 * k);
-        o = process_lane<NCH, true>(args, r[st & 1], own, slot);
-      } else {
-        o = process_lane<NCH>(args, r[st & 1], v[st & 1], slot);
-      }
-      store_sectors(o, lane, args.plain_sector, wt);
-      const uint32_t f = tf0 + st * kWave + lane;
-      nrec += store_result(args, f, f < args.n, o.res);
-      compiler_barrier();   // the next frame rewrites this lane's header window
-    }
-    tile = next;
-  }
-#ifdef XSKNF_TIMELINE
-  // stream done (last store issued), then its stores acknowledged
-  const unsigned long long tl1 = wall_clock64();
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  timeline_put(blockIdx.x * SW + wv, lane, tl0, tl1, tl_tiles, 0, 0, 0);
-#endif
-  publish_records(args, nrec, lane);
-}
-
-// ---- split kernel: headers by lane, payload by group ----------------------------
-//
-// The group kernels pay a frame's fixed work (descriptor, header parse, verdict,
-// check store) once per GROUP: LPF lanes redo it, and a short frame leaves most
-// of its group idle.  With a mix of lengths (IMIX) or medium frames (570 B)
-// that overhead, not HBM, sets the time.  Here a wave takes a tile of 64
-// consecutive frames in three phases:
-//  A. lane l owns frame l: it loads the frame's first W chunks (the header
-//     window), parses the header in its LDS slot, sums the window and, when the
-//     frame fits the window, finishes it exactly as the lane kernel does;
-//  B. the payload of the longer frames past the window is cut into ITEMS of one
-//     group pass (LPF lanes x NCH chunks) and the items are dealt to the wave's
-//     groups round robin, so the groups stay balanced whatever the mix; item
-//     sums meet in a per-frame LDS accumulator (ds_add);
-//  C. lane l folds its frame's total and stores the check (2 bytes in-line, or
-//     a record for the scatter pass).
-// The item list reuses the lane slots (dead after phase A).  Frames with more
-// items than a slot share holds take a whole-wave loop (correctness path).
-
-__device__ __forceinline__ uint32_t wave_excl_scan(uint32_t v, int lane, uint32_t &total) {
-  uint32_t x = v;
-#pragma unroll
-  for (int o = 1; o < kWave; o <<= 1) {
-    const uint32_t y = static_cast<uint32_t>(__shfl_up(static_cast<int>(x), o, kWave));
-    if (lane >= o) x += y;
-  }
-  total = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(x), kWave - 1));
-  return x - v;
-}
-
-__device__ __forceinline__ void lds_add_u32(uint32_t a, uint32_t v) {
-  __hip_atomic_fetch_add(reinterpret_cast<__attribute__((address_space(3))) uint32_t *>(static_cast<uintptr_t>(a)),
-                         v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-}
-
-__device__ __forceinline__ void lds_store_u16(uint32_t a, uint16_t v) {
-  *reinterpret_cast<__attribute__((address_space(3))) uint16_t *>(static_cast<uintptr_t>(a)) = v;
-}
-
-__device__ __forceinline__ uint32_t lds_u16(uint32_t a) {
-  return *reinterpret_cast<const __attribute__((address_space(3))) uint16_t *>(static_cast<uintptr_t>(a));
-}
-
-__device__ __forceinline__ uint32_t lds_byte(uint32_t a) {
-  return *reinterpret_cast<const lds_u8 *>(static_cast<uintptr_t>(a));
-}
-
-// Frame bytes rebuilt from integers (LDS) must be marked global, or hipcc
-// emits FLAT loads, which count in lgkmcnt too and serialize every LDS read
-// behind the loads in flight.
-typedef const __attribute__((address_space(1))) u32x4 *gchunk_ptr;
-
-__device__ __forceinline__ uint4 load_nt(gchunk_ptr p XSKNF_SITE) {
-#ifdef XSKNF_GUARD
-  p = guard_ld(p, 16, site);
-#endif
-  const u32x4 x = __builtin_nontemporal_load(p);
-  return make_uint4(x.x, x.y, x.z, x.w);
-}
-
-// A payload frame as phase B sees it: {fp lo, fp hi, len, u} in LDS.
-struct Payload {
-  gchunk_ptr cp;
-  int nch, lo, hi;
-  uint32_t wl, wh;
-};
-
-__device__ __forceinline__ Payload payload_of(uint4 m) {
-  Payload p;
-  const uintptr_t fp = (static_cast<uintptr_t>(m.y) << 32) | m.x;
-  const int rs = static_cast<int>(fp & 15);
-  p.cp = reinterpret_cast<gchunk_ptr>(fp - rs);
-  p.nch = static_cast<int>((static_cast<uint64_t>(rs) + m.z + 15) >> 4);
-  p.lo = rs + static_cast<int>(m.w);
-  p.hi = rs + static_cast<int>(m.z);
-  p.wl = (p.lo & 1) ? 0x01000100u : 0x00010001u;
-  p.wh = p.wl << 8 | p.wl >> 24;
-  return p;
-}
-
-// Phase B's loads are issued from inline asm with explicitly counted waits:
-// hipcc drains vmcnt to 0 at the top of any loop whose loads are consumed in a
-// later iteration, which would serialize the two-stage pipeline.  Each loaded
-// register is bound to its wait (an empty asm with a "+v" operand after the
-// s_waitcnt), so no use can move above the wait, and a stage that is never
-// consumed is drained before its registers can be reused.
-__device__ __forceinline__ u32x4 gload_nt_asm(gchunk_ptr p XSKNF_SITE) {
-#ifdef XSKNF_GUARD
-  p = guard_ld(p, 16, site);
-#endif
-  u32x4 x;   // nt: default-policy loads measured 1500 B 296 -> 344 us per step
-  asm volatile("global_load_dwordx4 %0, %1, off nt" : "=v"(x) : "v"(p) : "memory");
-  return x;
-}
-
-// One stage of phase B: U items per group, NCH chunks per lane each.
-template <int U, int NCH>
-struct ItemStage {
-  u32x4 t[U][NCH];
-  Payload pl[U];
-  uint32_t fi[U];
-  int c0[U];
-  bool ok[U];
-
-  template <int W, int LPF, int SPAN>
-  __device__ __forceinline__ void issue(uint32_t area, uint32_t mt, uint32_t it0, uint32_t total, int grp, int gl) {
-    constexpr int G = kWave / LPF;
-#pragma unroll
-    for (int q = 0; q < U; ++q) {
-      const uint32_t it = it0 + q * G + grp;
-      ok[q] = it < total;
-      const uint32_t e = lds_u16(area + 2 * min(it, total - 1));
-      fi[q] = e >> 8;
-      pl[q] = payload_of(lds_u128(mt + 16 * fi[q]));
-      c0[q] = W + static_cast<int>(e & 0xff) * SPAN;
-      if (!ok[q]) pl[q].hi = pl[q].lo;   // masked: sums nothing
-    }
-#pragma unroll
-    for (int q = 0; q < U; ++q)
-#pragma unroll
-      for (int k = 0; k < NCH; ++k) t[q][k] = gload_nt_asm(pl[q].cp + min(c0[q] + k * LPF + gl, pl[q].nch - 1));
-  }
-
-  // wait until at most N vector-memory operations younger than this stage's are outstanding
-  template <int N>
-  __device__ __forceinline__ void wait() {
-    static_assert(N >= 0 && N < 64, "vmcnt is 6 bits on gfx950");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-#pragma unroll
-    for (int q = 0; q < U; ++q)
-#pragma unroll
-      for (int k = 0; k < NCH; ++k) asm volatile("" : "+v"(t[q][k]));
-  }
-
-  template <int LPF>
-  __device__ __forceinline__ void consume(uint32_t ab, int gl) {
-    wait<U * NCH>();   // the other stage's loads stay in flight
-#pragma unroll
-    for (int q = 0; q < U; ++q) {
-      uint32_t blo = 0, bhi = 0;
-#pragma unroll
-      for (int k = 0; k < NCH; ++k) {
-        const uint4 v = make_uint4(t[q][k].x, t[q][k].y, t[q][k].z, t[q][k].w);
-        chunk_sum_fast(v, (c0[q] + k * LPF + gl) * 16, pl[q].lo, pl[q].hi, pl[q].wl, pl[q].wh, blo, bhi);
-      }
-      const uint32_t P = group_sum_last<LPF>(blo + (bhi << 8));
-      if (gl == LPF - 1 && ok[q]) lds_add_u32(ab + 4 * fi[q], P);
-    }
-  }
-};
-
-
-// The patch list: where the default shape (W = 8, two items in flight: 157
-// VGPRs, 3 waves per SIMD, so 3 blocks per CU) has LDS to spare, a deferred
-// check is not parked in `verdicts` but kept in the wave's LDS list, one
-// 8-byte entry per frame for its first kPatchTiles tiles: the check's 64-byte
-// sector as an index from the 64-byte-aligned UMEM base, and {valid, whole
-// sector, byte of the check in the sector, the check}.  The frame's final
-// verdict is stored in the tile's one verdict store, and the wave's patches
-// read neither records nor descriptors back: one round trip (the sectors)
-// instead of three.  launch_split sizes the grid so that no wave has more
-// tiles than its list (the code for tiles past it -- checks in-line -- is kept
-// as a fallback).  Past the list, checks were first parked as records in
-// `verdicts` for the wave to patch after its list (three round trips), then
-// written in-line; launches past their lists faulted with an illegal address
-// three times in full GPU suites, twice with the records and once in-line,
-// never alone or under the guard build.
-constexpr int kPatchTiles = 6;   // 6 x 64 x 8 B x 4 waves = 12 KiB per block
-constexpr int kPatchT = 2;       // tiles whose sectors are in flight together (3, 4: no gain, r02 ab_tail2, r04)
-// entry flags; kPatchInWin + window offset / 16 << 25 say where the sector lies
-// in the frame's header window (round 4 took such sectors from the slots
-// instead of reading them again: no gain, removed in round 5)
-constexpr uint32_t kPatchValid = 1u << 23, kPatchWhole = 1u << 22, kPatchInWin = 1u << 24;
-constexpr uint64_t kPatchMaxUmem = 1ull << 37;   // sector index: 32 bits (with margin)
-
-// Tiles in a wave's patch list: 16 x 2 items fit 3 waves per SIMD (6 tiles per
-// wave at 1M frames; 7 with the pool, whose faster waves take more units), 16 x
-// 3 fit 2 (8 tiles per wave); the other shapes keep no list.  A block of more
-// than 4 waves holds a whole CU's waves and shares the CU's tiles as a pool.
-// (Round 4's compact shape -- 4 waves per SIMD, phase-B scratch in the dead
-// window slots, 4-tile lists -- and its 16-wave static twin tied the default
-// and were removed in round 5: DESIGN 7.)
-constexpr bool pooled_split(int sw) { return sw > kWavesPerBlock; }
-// The parts each of a pool block's last tiles runs as: halves up to 4 KiB,
-// quarters for jumbo (W = 4; halves 1469.5-1470.7, eighths 1471.1-1471.5 vs
-// 1459.2-1461.0 us, NIC +10..14 us -- profiles/r05/ab/ab_jumbo_parts_r05jp.jsonl),
-// and how many: the last SW tiles, the last 3 SW for jumbo (2 SW with 16-unit
-// lists: 1445.2-1445.7 vs 1447.9-1448.8 us and 1455.4-1456.3 vs 1456.4-1459.2
-// on a second box, NIC -1..-2, ab_jumbo_split_tiles_r05jk.jsonl; 3 SW with
-// 20-unit lists: NIC -3.5..-4 us on two boxes, worst case -0.5..-1.7,
-// ab_jumbo_units20_r05j20.jsonl; as many as the lists hold, leaving the waves
-// no slack to balance: +50 us).
-constexpr uint32_t pool_parts(int w) { return w == 4 ? 4u : 2u; }
-// Tiles split at the end of a pool block of SW waves (the last 8 or 16 tiles
-// halved instead of 12 at 1500 B: 276.5-277.5 and 277.5-278.5 vs 277.3-278.3
-// us, NIC +0.5..1 -- profiles/r05/ab/ab_halves_tiles_*).
-constexpr uint32_t pool_split_tiles(int w, int sw) { return w == 4 ? 3u * sw : static_cast<uint32_t>(sw); }
-// The most tiles one pool block may hold so that its units fit its waves'
-// patch lists (SW x PT entries): bt tiles, the last pool_split_tiles of them in
-// pool_parts units each, are bt + (parts - 1) x split units.  launch_split sizes
-// the grid by it and the kernel asserts the same count, so the two cannot drift.
-constexpr uint32_t pool_block_tiles_max(int w, int sw, int pt) {
-  return static_cast<uint32_t>(sw * pt) - (pool_parts(w) - 1) * pool_split_tiles(w, sw);
-}
-
-// Pool guard: a pooled wave whose patch list is full claims no more units, so
-// a grid too small for the batch would leave units unclaimed (their frames
-// unsummed).  launch_split's bound makes that unreachable; should it ever be
-// reached, each block with more units than its waves' lists hold counts here
-// at its start, and each wave that waits in vain for a unit's mark in the
-// patch queue counts too (xsknf_gpu_pool_guard_trips reads it).
-__device__ unsigned int g_pool_guard_trips;
-
-// The pooled jumbo shape (W = 4, 16 x 3 items, one 8-wave block per CU) keeps
-// a 20-unit list (80 KiB of its block's 151 KiB; 16 units until the late
-// round-5 A/B above): with every check deferred
-// (fused_stores 2 + 16) the block's queue patches them in the launch instead of
-// a scatter_checks pass (round 5: 9000 B 1448.4-1449.3 vs 1455.9-1457.9 us and
-// 1457.2-1458.1 vs 1461.6-1462.9 on a second box, NIC checks -4 us;
-// profiles/r05/ab/).
-constexpr int kJumboPatchUnits = 20;
-template <int W, int NCH, int U, bool kPool>
-constexpr int patch_list_tiles() {
-  if constexpr (W == 4 && NCH == 3 && U >= 2 && kPool) return kJumboPatchUnits;
-  return (W == 8 && U >= 2) ? (NCH == 2 ? (kPool ? 7 : kPatchTiles) : 8) : 0;
-}
-
-__device__ __forceinline__ uint2 patch_entry(const KernelArgs &a, const FrameRef &r, int u, uint16_t c, int wbytes) {
-  const uintptr_t f0 = reinterpret_cast<uintptr_t>(r.fp);
-  const uintptr_t ck = f0 + static_cast<uintptr_t>(u) + 6;
-  const uintptr_t sec = ck & ~static_cast<uintptr_t>(63);
-  const uintptr_t base = reinterpret_cast<uintptr_t>(a.umem) & ~static_cast<uintptr_t>(63);
-  const bool whole = sec >= f0 && sec + 64 <= f0 + static_cast<uintptr_t>(r.len) && (ck & 63) != 63;
-  const uintptr_t c0 = reinterpret_cast<uintptr_t>(r.cp);
-  const bool in_win = whole && sec >= c0 && sec + 64 <= c0 + static_cast<uintptr_t>(wbytes);
-  return make_uint2(static_cast<uint32_t>((sec - base) >> 6),
-                    kPatchValid | (whole ? kPatchWhole : 0u) | static_cast<uint32_t>((ck & 63) << 16) | c |
-                        (in_win ? kPatchInWin | static_cast<uint32_t>((sec - c0) >> 4) << 25 : 0u));
-}
-
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void lds_store_u64(uint32_t a, uint2 v) {
-  const u32x2 x = {v.x, v.y};
-  *reinterpret_cast<__attribute__((address_space(3))) u32x2 *>(static_cast<uintptr_t>(a)) = x;
-}
-
-__device__ __forceinline__ uint2 lds_u64(uint32_t a) {
-  const u32x2 x = *reinterpret_cast<const __attribute__((address_space(3))) u32x2 *>(static_cast<uintptr_t>(a));
-  return make_uint2(x.x, x.y);
-}
-
-// The wave's patch list (ntiles tiles of 64 entries at LDS `pl`): 16 frames per
-// round, 4 lanes per frame, each frame's sector read and rewritten whole (one
-// non-temporal 64-byte store of 4 lanes), or its 2 check bytes where the sector
-// leaves the frame.  kPatchT tiles' sectors are in flight together.
-__device__ __forceinline__ void tail_patch_list(const KernelArgs &args, uint32_t pl, int ntiles, int lane) {
-  const int piece = lane & 3;
-  uint8_t *const base = args.umem - (reinterpret_cast<uintptr_t>(args.umem) & 63);   // keeps global addressing
-  constexpr int T = kPatchT;
-  for (int t0 = 0; t0 < ntiles; t0 += T) {
-    uint4 v[T][4];
-    uint8_t *mine[T][4];
-    uint32_t info[T][4];
-#pragma unroll
-    for (int t = 0; t < T; ++t) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const uint2 e = t0 + t < ntiles ? lds_u64(pl + 8 * ((t0 + t) * kWave + 16 * k + (lane >> 2))) : make_uint2(0, 0);
-        info[t][k] = e.y;
-        uint8_t *sec = base + (static_cast<uint64_t>(e.x) << 6);
-        const bool whole = (e.y & (kPatchValid | kPatchWhole)) == (kPatchValid | kPatchWhole);
-        mine[t][k] = whole ? sec + 16 * piece : sec + ((e.y >> 16) & 63);
-        if (whole)
-          v[t][k] = load_nt(reinterpret_cast<const uint4 *>(mine[t][k]));
-      }
-    }
-#pragma unroll
-    for (int t = 0; t < T; ++t) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const uint32_t c = info[t][k] & 0xffffu;
-        if ((info[t][k] & (kPatchValid | kPatchWhole)) == (kPatchValid | kPatchWhole)) {
-          const int o = static_cast<int>((info[t][k] >> 16) & 63) - 16 * piece;
-          uint4 w = put_byte(v[t][k], o, c);
-          w = put_byte(w, o + 1, c >> 8);
-          store_nt16(mine[t][k], w);   // plain (write-back) stores: 1500 B +20 us, IMIX +8 (r02 ab_tail2)
-        } else if ((info[t][k] & kPatchValid) && piece == 0) {
-          XSKNF_GST(mine[t][k], 2) {
-            mine[t][k][0] = static_cast<uint8_t>(c);
-            mine[t][k][1] = static_cast<uint8_t>(c >> 8);
-          }
-        }
-      }
-    }
-  }
-}
-
-
-// One item per group in flight (U = 1) fits 4 waves per SIMD (<= 128 VGPRs),
-// which the LDS footprint also allows (4 blocks per CU): measured IMIX / 570 B
-// +8-11 % from 2 -> 3 waves per SIMD, so the register budget is pinned.
-template <int W, int LPF, int NCH, int U, bool TL, int SW>
-__global__ __launch_bounds__(SW * kWave) __attribute__((amdgpu_waves_per_eu(U == 1 ? 4 : 1)))
-void checksum_kernel_split(const KernelArgs args) {
-  static_assert(W >= 4 && (W <= kHdrChunks || W == 8), "header window");
-  static_assert(!TL || W == 4 || W == 8, "transposed window load: W lanes x 16 B per frame");
-  static_assert(kWave % LPF == 0 && LPF >= 4, "group shape");
-  constexpr int G = kWave / LPF;
-  constexpr int SPAN = LPF * NCH;                          // chunks per item
-  constexpr int kSlot = 16 * W > kLaneSlot ? 16 * W : kLaneSlot;   // per-lane header window
-  constexpr int kSlotArea = kWave * kSlot;                 // bytes per wave
-  constexpr int kItemCap = 256;                            // items per round of phase B
-  constexpr uint32_t kItemsPerFrame = 255;                 // u8 pass index; more: whole-wave loop
-  constexpr bool kPool = pooled_split(SW);   // one block per CU: its waves share the CU's tiles
-  __shared__ __attribute__((aligned(16))) uint8_t slots[SW][kSlotArea];
-  __shared__ __attribute__((aligned(16))) uint16_t itemq[SW][kItemCap];
-  __shared__ __attribute__((aligned(16))) uint4 meta[SW][kWave];
-  __shared__ __attribute__((aligned(16))) uint32_t accb[SW][kWave];
-  // (jumbo's list: each wave patching its own list after its last unit tied the scatter
-  // pass, 1463 vs 1461 us -- profiles/r02/ab_jumbo_tail.jsonl; from the block's queue it is ahead)
-  constexpr int PT = patch_list_tiles<W, NCH, U, kPool>();
-  __shared__ __attribute__((aligned(16))) uint2 plist[SW][PT > 0 ? PT * kWave : 1];
-
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-  const int grp = lane / LPF, gl = lane % LPF;
-  const uint32_t area = lds_addr(&slots[wv][0]);
-  const uint32_t slot = area + kSlot * lane;
-  const uint32_t mt = lds_addr(&meta[wv][0]);
-  const uint32_t ab = lds_addr(&accb[wv][0]);
-  const uint32_t iq = lds_addr(&itemq[wv][0]);
-  const uint32_t waves = gridDim.x * SW;
-  const uint32_t last = args.n - 1;
-// Streaming waves issue ahead of patching ones: priority 1 until the wave's
-// last unit, 0 for its patches (with the patch queue below: 1500 B -0.9..-1.5
-// us, its NIC traffic -3 us, other sizes level -- profiles/r04/ab/ab_patch_prio_*)
-  __builtin_amdgcn_s_setprio(1);
-
-  uint32_t nrec = 0;
-#ifdef XSKNF_TIMELINE
-  const unsigned long long tl0 = wall_clock64();
-  unsigned long long tl_a = 0, tl_p = 0, tl_b = 0, tl_t = 0;
-#define XSKNF_TL_MARK(acc) do { const unsigned long long n_ = wall_clock64(); acc += n_ - tl_t; tl_t = n_; } while (0)
-#define XSKNF_TL_START() do { tl_t = wall_clock64(); } while (0)
-#else
-#define XSKNF_TL_START() do { } while (0)
-#define XSKNF_TL_MARK(acc) do { } while (0)
-#endif
-  const uint32_t pl = lds_addr(&plist[wv][0]);
-  const bool list_ok = PT > 0 && args.tail_scatter && args.umem_size < kPatchMaxUmem;
-  int it = 0;              // tiles done by this wave
-  bool any_entry = false;  // wave-uniform: the patch list holds an entry
-  // The wave's tiles: `tile`, then `tn`, `tnn` (kNoTile: none).
-  // * SW = 4 (several blocks per CU): every waves-th tile from the wave's index,
-  //   descriptors two tiles ahead.
-  // * kPool (one block holds every wave of its CU: SW = 12, or 8 for jumbo):
-  //   the block's tiles, every nb-th from the block index, are a pool of units
-  //   its waves draw from -- the first by wave index, each later one claimed
-  //   through an LDS counter when the wave starts a unit, its descriptors
-  //   loaded while that unit streams.  A CU's waves do not stream equally fast
-  //   (three 4-wave blocks per CU: the third block's waves ended their streams
-  //   ~40 us after the first two's at 1500 B, tools/timeline.py), and from a
-  //   shared pool the faster ones take more units.  A unit past the wave's
-  //   patch list writes its checks in-line.  (Per-XCD global counters were
-  //   tried: a device-scope atomic retires in vmcnt order, and each round trip
-  //   held up the next load wait -- 1500 B 347 vs 291 us.)
-  const uint32_t ntiles = (args.n + kWave - 1) / kWave;
-  __shared__ uint32_t pool_next;
-  const uint32_t nb = gridDim.x;
-  const uint32_t bt = ntiles > blockIdx.x ? (ntiles - blockIdx.x + nb - 1) / nb : 0u;   // the block's tiles
-  const auto tile_of = [&](uint32_t k) { return blockIdx.x + k * nb; };
-  // The pool's units: the block's tiles, except that its last SW tiles (2 SW
-  // for jumbo) run as kParts parts each, so the waves' streams end closer together: halves up to
-  // 4 KiB (quarters there: 570 B 165 vs 151 us, 1024 B 213 vs 205 --
-  // profiles/r02/ab_pool.jsonl), quarters for jumbo tiles (W = 4), which
-  // stream for ~160 us each.  (Whole tiles only: IMIX level, 1500 B +6-7 us;
-  // profiles/r04/ab/ab_pool_no_halves*.)
-  constexpr uint32_t kParts = pool_parts(W);
-  const uint32_t nsplit = kPool ? min(bt, pool_split_tiles(W, SW)) : 0u;
-  const uint32_t nfull = bt - nsplit;
-  const uint32_t units = nfull + kParts * nsplit;
-  const auto pool_unit = [&](uint32_t p) { return p < units ? p : kNoTile; };
-  // first frame and frame count of unit / static tile u
-  const auto unit_f0 = [&](uint32_t u) -> uint32_t {
-    if constexpr (kPool) {
-      if (u < nfull) return tile_of(u) * kWave;
-      const uint32_t h = u - nfull;
-      return tile_of(nfull + h / kParts) * kWave + (h % kParts) * (kWave / kParts);
-    } else {
-      return u * kWave;
-    }
-  };
-  const auto unit_cnt = [&](uint32_t u) -> uint32_t { return kPool && u >= nfull ? kWave / kParts : kWave; };
-  bool pool_live = kPool;   // wave-uniform: no failed dequeue yet
-  uint32_t tile, tn, tnn;   // pool units (kPool) or tiles
-  if constexpr (kPool) {
-    // a wave holds at most the unit it sums and the next (claimed three ahead,
-    // the waves of a block ended 43 us apart at 1500 B: 284.5 vs 279.2 us;
-    // claimed when the unit's payload starts rather than at its start: 1500 B a
-    // tie, 570 B 149.1 vs 146.7, IMIX 118.5 vs 115.9 -- profiles/r02/ab_pool.jsonl)
-    tile = pool_unit(wv);
-    tn = tnn = kNoTile;
-    if (threadIdx.x == 0) pool_next = SW;
-    __syncthreads();
-  } else {
-    const uint32_t t0 = blockIdx.x * SW + wv;
-    tile = t0 < ntiles ? t0 : kNoTile;
-    tn = t0 + waves < ntiles ? t0 + waves : kNoTile;
-    tnn = t0 + 2 * waves < ntiles ? t0 + 2 * waves : kNoTile;
-  }
-  // One patch queue per block (the pooled shapes) instead of each wave patching its own list
-  // after its last unit: a wave publishes each finished unit's list (its index,
-  // or a null mark for a unit with nothing to patch), and a wave whose stream
-  // is done takes the next published unit of ANY wave of the block, so the
-  // block's last stream is followed by one unit's patches, not by its wave's
-  // whole list.  Every wave publishes one mark per unit; the block's count of
-  // units is known, so the consumers' loop ends; the wait for a mark is bounded
-  // by the clock.  Measured alone: 1500 B -0.8..-1.5 us, the launch still ends
-  // ~7 us after its last stream (profiles/r04/ab/ab_patch_queue_*); with the
-  // streaming waves' priority the product's since round 4.  The static 4-wave
-  // blocks (IMIX) keep each wave patching its own list (a queue there: IMIX +1
-  // us, profiles/r04/ab/ab_patch_queue_static_bench.jsonl).
-  constexpr bool kShared = PT > 0 && kPool;
-  constexpr uint32_t kPQ = kShared ? SW * PT : 1;   // marks: the grid is sized so a block has <= SW * PT units
-  constexpr uint32_t kPQNull = 0xffffu;
-  static_assert(!kShared || pool_block_tiles_max(W, SW, PT) + (pool_parts(W) - 1) * pool_split_tiles(W, SW) == kPQ,
-                "a pool block at launch_split's tile bound has exactly as many units as its lists hold");
-  __shared__ uint32_t pq_tail, pq_head;
-  __shared__ uint32_t pq[kPQ];
-  const bool shared_on = kShared && list_ok;   // block-uniform
-  bool pq_full = false;                        // wave-uniform: a mark found no room
-  uint32_t block_units = 0;
-  if constexpr (kShared) {
-    block_units = units;
-    // more units than the waves' lists hold: the waves stop claiming once their
-    // lists are full, so units are left unclaimed (never, by launch_split's bound;
-    // the same count the marks below would wait for in vain)
-    if (threadIdx.x == 0 && shared_on && units > kPQ)
-      __hip_atomic_fetch_add(&g_pool_guard_trips, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (threadIdx.x == 0) pq_tail = pq_head = 0;
-    for (uint32_t i = threadIdx.x; i < kPQ; i += SW * kWave) pq[i] = 0;
-    __syncthreads();
-  }
-  const auto desc_of = [&](uint32_t t) {
-    return *XSKNF_GLD(reinterpret_cast<const uint4 *>(args.descs + (t == kNoTile ? last : min(unit_f0(t) + lane, last))), 16);
-  };
-  // descriptors travel two tiles ahead (static), one unit ahead (kPool)
-  uint4 d = desc_of(tile);
-  uint4 dn = kPool ? d : desc_of(tn);
-  while (tile != kNoTile) {
-    XSKNF_TL_START();
-    if constexpr (kPool) {   // claim the next unit, and load its descriptors while this one streams
-      uint32_t dq = 0;
-      // a wave whose patch list is full claims no more: launch_split sizes the
-      // grid so that the lists of a block's waves hold all of its units
-      if (list_ok && it + 1 >= PT) pool_live = false;
-      if (pool_live && lane == 0) dq = __hip_atomic_fetch_add(&pool_next, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      tn = pool_live ? pool_unit(static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(dq), 0))) : kNoTile;
-      pool_live = tn != kNoTile;
-      dn = desc_of(tn);
-    }
-
-    const uint32_t f0 = unit_f0(tile), cnt = unit_cnt(tile);
-    const uint32_t f = lane < cnt ? f0 + lane : args.n;   // lanes past a half unit hold no frame
-    const FrameRef r = lane_ref(args, d, f);
-    uint4 v[W];
-    if constexpr (TL) {
-      // transposed: lanes W*i .. W*i+W-1 load the window of frame (64/W)*p + i
-      // (p = 0..W-1), one coalesced 16*W-byte request per frame instead of W
-      // 16-byte ones, and drop it in that frame's slot
-      constexpr int FPI = kWave / W;   // frames per load instruction
-      const uintptr_t cpv = reinterpret_cast<uintptr_t>(r.cp);
-      u32x4 x[W];
-#pragma unroll
-      for (int p = 0; p < W; ++p) {
-        const int g = FPI * p + lane / W;
-        const uint32_t lo = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(g << 2, static_cast<int>(cpv)));
-        const uint32_t hi = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(g << 2, static_cast<int>(cpv >> 32)));
-        const int nc = __builtin_amdgcn_ds_bpermute(g << 2, r.nch);
-        const gchunk_ptr cp = reinterpret_cast<gchunk_ptr>((static_cast<uintptr_t>(hi) << 32) | lo);
-        x[p] = *XSKNF_GLD(cp + min(lane % W, nc - 1), 16);   // default policy: nt measured 64 B 39 -> 55 us, 1500 B 292 -> 308
-      }
-      compiler_barrier();
-#pragma unroll
-      for (int p = 0; p < W; ++p)
-        lds_store_u128(area + kSlot * (FPI * p + lane / W) + 16 * (lane % W), make_uint4(x[p].x, x[p].y, x[p].z, x[p].w));
-      compiler_barrier();
-#pragma unroll
-      for (int k = 0; k < W; ++k) v[k] = lds_u128(slot + 16 * k);
-    } else {
-      load_lane<W>(r, v);
-    }
-    XSKNF_TL_MARK(tl_a);
-    const uint4 dnn = kPool ? d : desc_of(tnn);
-    const bool to_list = list_ok && it < PT;   // wave-uniform
-    // per-tile store policy, as the register kernel: long frames defer their
-    // checks only where they are at least half of the tile
-    // (a wave's tiles past its patch list: in-line)
-    uint32_t defer_min = args.tail_scatter && !to_list ? kNoDefer : args.defer_min_len;
-    if (defer_min != kNoDefer && defer_min != 0 && !args.no_scatter) {
-      const uint32_t nlong = static_cast<uint32_t>(__builtin_popcountll(
-          __builtin_amdgcn_ballot_w64(f < args.n && d.z >= defer_min)));
-      const uint32_t nlive = f0 < args.n ? min(cnt, args.n - f0) : 0u;
-      if (kDeferTileK * nlong < nlive) defer_min = kNoDefer;
-    }
-
-    // ---- phase A: header, window sum, short frames finished ----
-    compiler_barrier();
-    if constexpr (!TL) {
-#pragma unroll
-      for (int k = 0; k < W; ++k) lds_store_u128(slot + 16 * k, v[k]);
-    }
-    compiler_barrier();
-    {  // header bytes past the window (large ihl, or a frame start late in its chunk)
-      const int u0 = 14 + 4 * static_cast<int>(lds_byte(slot + r.rs + 14) & 0x0f);
-      const int need = min((r.rs + u0 + 8 + 15) >> 4, r.nch);
-      for (int k = W; k < need; ++k) lds_store_u128(slot + 16 * k, *XSKNF_GLD(r.cp + k, 16));
-    }
-    compiler_barrier();
-    const Header h = parse_header(slot + r.rs);
-    compiler_barrier();
-    bool do_sum;
-    const int32_t verdict = verdict_of(r, h, args.fwd_verdict, do_sum);
-    const int lo = r.rs + h.u, hi = r.rs + r.len;
-    const uint32_t wl = (lo & 1) ? 0x01000100u : 0x00010001u;
-    const uint32_t wh = wl << 8 | wl >> 24;
-    uint32_t acc_lo = 0, acc_hi = 0;
-#pragma unroll
-    for (int k = 0; k < W; ++k) chunk_sum(v[k], 16 * k, lo, hi, wl, wh, acc_lo, acc_hi);
-    const uint32_t PA = acc_lo + (acc_hi << 8);
-    const bool more = do_sum && r.nch > W && args.payload_mult != 0;   // payload past the window
-    const uint32_t items = more ? static_cast<uint32_t>((r.nch - W + SPAN - 1) / SPAN) : 0u;
-    const bool huge = items > kItemsPerFrame;
-    int32_t res = r.exists ? verdict : 0;
-    LaneOut o = {res, false, slot, r.fp};
-    uint2 ent = make_uint2(0, 0);
-    if (do_sum && !more && check_changes(args, h, check_of(h, PA, args.payload_mult))) {
-      const uint16_t c = check_of(h, PA, args.payload_mult);
-      if (static_cast<uint32_t>(r.len) >= defer_min) {
-        if (to_list) ent = patch_entry(args, r, h.u, c, 16 * W);
-        else res = static_cast<int32_t>(kRecTag | (static_cast<uint32_t>(h.u) << 16) | c);
-      } else {
-        const uintptr_t f0 = reinterpret_cast<uintptr_t>(r.fp);
-        const uintptr_t ck = f0 + h.u + 6;
-        const uintptr_t sec = ck & ~static_cast<uintptr_t>(63);
-        const uintptr_t c0 = reinterpret_cast<uintptr_t>(r.cp);
-        if (args.sector_stores && sec >= f0 && sec + 64 <= f0 + r.len && (ck & 63) != 63 && sec >= c0 &&
-            sec + 64 <= c0 + 16 * W) {
-          const uint32_t at = slot + static_cast<uint32_t>(ck - c0);
-          lds_store_u8(at, static_cast<uint8_t>(c));
-          lds_store_u8(at + 1, static_cast<uint8_t>(c >> 8));
-          o.sector = true;
-          o.lds_sec = slot + static_cast<uint32_t>(sec - c0);
-          o.gsec = r.fp + static_cast<intptr_t>(sec - f0);
-        } else {
-          XSKNF_GST(r.fp + h.u + 6, 2) *reinterpret_cast<uint16_t *>(r.fp + h.u + 6) = c;   // :108
-        }
-      }
-    }
-    store_sectors(o, lane, args.plain_sector);
-    const uint32_t part = h.pseudo + args.payload_mult * (PA - h.old_check);
-
-    // ---- phase B: payload items of the longer frames ----
-    XSKNF_TL_MARK(tl_p);
-    if (__builtin_amdgcn_ballot_w64(more)) {
-      const uintptr_t fpv = reinterpret_cast<uintptr_t>(r.fp);
-      lds_store_u128(mt + 16 * lane, make_uint4(static_cast<uint32_t>(fpv), static_cast<uint32_t>(fpv >> 32),
-                                                static_cast<uint32_t>(r.len), static_cast<uint32_t>(h.u)));
-      lds_store_u32(ab + 4 * lane, 0u);
-      uint32_t total;
-      const uint32_t mine = huge ? 0u : items;
-      const uint32_t start = wave_excl_scan(mine, lane, total);
-      // the wave's item list, in rounds of kItemCap: two stages of U items per
-      // group, ping-pong, so the loads of stage s+1 are in flight while stage s
-      // is summed (a stage past the list reloads the last item, masked:
-      // straight-line code keeps vmcnt counted, not drained)
-      for (uint32_t r0 = 0; r0 < total; r0 += kItemCap) {
-        const uint32_t nr = min(total - r0, static_cast<uint32_t>(kItemCap));
-        const uint32_t k0 = r0 > start ? r0 - start : 0u;
-        const uint32_t k1 = r0 + nr > start ? min(mine, r0 + nr - start) : 0u;
-        compiler_barrier();   // the previous round's list has been consumed
-        for (uint32_t k = k0; __builtin_amdgcn_ballot_w64(k < k1); ++k)
-          if (k < k1) lds_store_u16(iq + 2 * (start + k - r0), static_cast<uint16_t>((lane << 8) | k));
-        compiler_barrier();
-        ItemStage<U, NCH> sa, sb;
-        sa.template issue<W, LPF, SPAN>(iq, mt, 0, nr, grp, gl);
-        for (uint32_t it0 = 0;;) {
-          sb.template issue<W, LPF, SPAN>(iq, mt, it0 + G * U, nr, grp, gl);
-          sa.template consume<LPF>(ab, gl);
-          if ((it0 += G * U) >= nr) { sb.template wait<0>(); break; }
-          sa.template issue<W, LPF, SPAN>(iq, mt, it0 + G * U, nr, grp, gl);
-          sb.template consume<LPF>(ab, gl);
-          if ((it0 += G * U) >= nr) { sa.template wait<0>(); break; }
-        }
-      }
-      // frames past the item budget: the whole wave sums each one
-      for (uint64_t hm = __builtin_amdgcn_ballot_w64(huge); hm; hm &= hm - 1) {
-        const int fl = __builtin_ctzll(hm);
-        const Payload pl = payload_of(lds_u128(mt + 16 * fl));
-        uint32_t blo = 0, bhi = 0;
-        for (int c = W + lane; __builtin_amdgcn_ballot_w64(c < pl.nch); c += kWave)
-          chunk_sum_fast(load_nt(pl.cp + min(c, pl.nch - 1)), c * 16, pl.lo, pl.hi, pl.wl, pl.wh, blo, bhi);
-        const uint32_t P = group_sum_last<kWave>(blo + (bhi << 8));
-        if (lane == kWave - 1) lds_add_u32(ab + 4 * fl, P);
-      }
-      compiler_barrier();
-      XSKNF_TL_MARK(tl_b);
-      // ---- phase C: fold, check, store ----
-      // an in-line check whose 64-byte sector lies in the frame and the window
-      // is written as that whole sector: patched in the lane's slot (the window
-      // is still there) and stored by the wave, as in phase A
-      LaneOut oc = {0, false, slot, r.fp};
-      const uint32_t s = part + args.payload_mult * lds_i32(ab + 4 * lane);   // :92-103
-      const uint16_t c = static_cast<uint16_t>(~static_cast<uint16_t>((s & 0xffffu) + (s >> 16)));
-      if (more && check_changes(args, h, c)) {
-        const uintptr_t f0 = reinterpret_cast<uintptr_t>(r.fp);
-        const uintptr_t ck = f0 + h.u + 6;
-        const uintptr_t sec = ck & ~static_cast<uintptr_t>(63);
-        const uintptr_t c0 = reinterpret_cast<uintptr_t>(r.cp);
-        if (static_cast<uint32_t>(r.len) >= defer_min) {
-          if (to_list) ent = patch_entry(args, r, h.u, c, 16 * W);
-          else res = static_cast<int32_t>(kRecTag | (static_cast<uint32_t>(h.u) << 16) | c);
-        } else if (args.sector_stores && sec >= f0 && sec + 64 <= f0 + r.len && (ck & 63) != 63 &&
-                   sec >= c0 && sec + 64 <= c0 + 16 * W) {
-          const uint32_t at = slot + static_cast<uint32_t>(ck - c0);
-          lds_store_u8(at, static_cast<uint8_t>(c));
-          lds_store_u8(at + 1, static_cast<uint8_t>(c >> 8));
-          oc.sector = true;
-          oc.lds_sec = slot + static_cast<uint32_t>(sec - c0);
-          oc.gsec = r.fp + static_cast<intptr_t>(sec - f0);
-        } else {
-          XSKNF_GST(r.fp + h.u + 6, 2) *reinterpret_cast<uint16_t *>(r.fp + h.u + 6) = c;   // :108
-        }
-      }
-      store_sectors(oc, lane, args.plain_sector);
-      compiler_barrier();
-    }
-    nrec += store_result(args, f, f < args.n, res);
-    if (to_list) {
-      lds_store_u64(pl + 8 * (it * kWave + lane), ent);
-      any_entry |= __builtin_amdgcn_ballot_w64(ent.y != 0) != 0;
-    }
-    if constexpr (kShared) {
-      if (shared_on) {   // publish this unit's list (the entries are in LDS before the mark)
-        const bool tany = to_list && __builtin_amdgcn_ballot_w64(ent.y != 0) != 0;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        uint32_t slot = 0;
-        if (lane == 0) slot = __hip_atomic_fetch_add(&pq_tail, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        slot = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(slot), 0));
-        if (slot < kPQ) {
-          if (lane == 0)
-            __hip_atomic_store(&pq[slot], tany ? (static_cast<uint32_t>(wv) << 8 | static_cast<uint32_t>(it)) + 1u : kPQNull,
-                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        } else {
-          pq_full = true;   // (never: the grid is sized) the wave patches its whole list itself at the end
-        }
-      }
-    }
-    ++it;
-    compiler_barrier();   // the next tile rewrites the slots
-    if constexpr (kPool) {
-      tile = tn;
-      d = dn;
-    } else {
-      const uint32_t t3 = tnn != kNoTile && tnn + waves < ntiles ? tnn + waves : kNoTile;
-      tile = tn;
-      tn = tnn;
-      tnn = t3;
-      d = dn;
-      dn = dnn;
-    }
-  }
-#ifdef XSKNF_TIMELINE
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  const unsigned long long tl1 = wall_clock64();
-#endif
-  __builtin_amdgcn_s_setprio(0);
-  if (args.tail_scatter) {
-    if constexpr (kShared) {
-      if (shared_on) {
-        const uint64_t tw0 = wall_clock64();
-        for (;;) {
-          uint32_t h = 0;
-          if (lane == 0) h = __hip_atomic_fetch_add(&pq_head, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          h = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(h), 0));
-          if (h >= block_units || h >= kPQ) break;
-          uint32_t m = 0;
-          for (;;) {
-            m = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(
-                __hip_atomic_load(&pq[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP))));
-            if (m != 0 || wall_clock64() - tw0 > 2000000ull) break;   // 20 ms: never, unless units went unclaimed
-            __builtin_amdgcn_s_sleep(2);
-          }
-          if (m == 0) {   // a unit no wave claimed: its frames are unsummed (never, by the grid bound)
-            if (lane == 0) __hip_atomic_fetch_add(&g_pool_guard_trips, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            break;
-          }
-          if (m != kPQNull) {
-            const uint32_t w2 = (m - 1) >> 8, t2 = (m - 1) & 0xffu;
-            tail_patch_list(args, lds_addr(&plist[w2][0]) + 8 * t2 * kWave, 1, lane);
-          }
-        }
-      }
-    }
-    if (any_entry && (!shared_on || pq_full)) tail_patch_list(args, pl, min(it, PT), lane);
-  } else {
-    publish_records(args, nrec, lane);
-  }
-#ifdef XSKNF_TIMELINE
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  timeline_put(blockIdx.x * SW + wv, lane, tl0, tl1, it, tl_a, tl_p, tl_b);
-#endif
-}
-
-
-
-// ---- phase 2: write-only pass of the parked checks (:108) and verdicts -------
-//
-// Measured on MI355X (tools/hbm_probe): a scattered 2-byte write costs as much
-// as a read-modify-write of its 64-byte memory sector, and writes left dirty in
-// the caches are written back during the NEXT batch's read pass, where they
-// cost far more.  So this pass uses non-temporal stores (written back now) and,
-// where the aligned 64-byte sector holding the check lies entirely inside the
-// frame, rewrites the whole sector -- its 64 bytes re-read and patched -- as ONE
-// store instruction of 4 adjacent lanes (a full-sector write, no RMW): 4 lanes
-// per frame.  Otherwise (sector crosses the frame edge, or the check straddles
-// two sectors) it writes the 2 check bytes alone.  Only this frame's own bytes
-// are ever rewritten (with their own values), so frames never race.
-//
-// Two shapes, picked per launch from the record count the summing kernel
-// leaves in g_rec_count: dense (4 lanes per frame over the grid) and sparse
-// (per-wave scan + compaction).
-
-// Rewrite one parked check: lane `piece` (0..3) of the record's 4 lanes.
-__device__ __forceinline__ void rewrite_check(const KernelArgs &args, uint32_t f, uint32_t r,
-                                              const xsknf_gpu_desc &d, int piece) {
-  uint8_t *fp = args.umem + umem_offset(d.addr);
-  uint8_t *chk = fp + ((r >> 16) & 0x7f) + 6;
-  const uint16_t c = static_cast<uint16_t>(r);
-  uint8_t *sec = chk - (reinterpret_cast<uintptr_t>(chk) & 63);   // keeps global addressing
-  const bool whole = sec >= fp && sec + 64 <= fp + d.len && (reinterpret_cast<uintptr_t>(chk) & 63) != 63;
-  if (whole) {
-    uint8_t *mine = sec + 16 * piece;
-    const int o = static_cast<int>(chk - mine);          // check offset in my 16-B piece (-1..63)
-    uint4 v = load_nt(reinterpret_cast<const uint4 *>(mine));
-    v = put_byte(v, o, c);
-    v = put_byte(v, o + 1, c >> 8);
-    store_nt16(mine, v);
-  } else if (piece == 0) {
-    XSKNF_GST(chk, 2) {
-      chk[0] = static_cast<uint8_t>(c);
-      chk[1] = static_cast<uint8_t>(c >> 8);
-    }
-  }
-  if (piece == 0) {
-    XSKNF_GST(args.verdicts + f, 4) args.verdicts[f] = args.fwd_verdict;
-  }
-}
-
-// Dense records (>= 1/4 of the frames): 4 lanes per frame over the whole grid;
-// each lane's record and descriptor loads are independent of any scan.  A lane
-// takes kScatterU frames per round, so each round costs two dependent memory
-// round trips (record + descriptor, then the sector) for kScatterU frames
-// rather than per frame: the pass is latency-bound, not bandwidth-bound.
-constexpr int kScatterU = 4;
-
-__device__ __forceinline__ void scatter_dense(const KernelArgs &args) {
-  const uint32_t nthreads = gridDim.x * kBlock;
-  const uint32_t total = 4 * args.n;
-  for (uint32_t t0 = blockIdx.x * kBlock + threadIdx.x; t0 < total; t0 += kScatterU * nthreads) {
-    uint32_t r[kScatterU];
-    xsknf_gpu_desc d[kScatterU];
-#pragma unroll
-    for (int k = 0; k < kScatterU; ++k) {
-      const uint32_t f = min(t0 + k * nthreads, total - 1) >> 2;
-      r[k] = static_cast<uint32_t>(*XSKNF_GLD(args.verdicts + f, 4));
-      d[k] = *XSKNF_GLD(args.descs + f, 16);
-    }
-    uint4 v[kScatterU];
-    uint8_t *mine[kScatterU];
-    int o[kScatterU];
-    bool whole[kScatterU], rec[kScatterU];
-#pragma unroll
-    for (int k = 0; k < kScatterU; ++k) {
-      const uint32_t t = t0 + k * nthreads;
-      rec[k] = t < total && (r[k] & kRecTagMask) == kRecTag;
-      uint8_t *fp = args.umem + umem_offset(d[k].addr);
-      uint8_t *chk = fp + ((r[k] >> 16) & 0x7f) + 6;
-      uint8_t *sec = chk - (reinterpret_cast<uintptr_t>(chk) & 63);   // keeps global addressing
-      whole[k] = rec[k] && sec >= fp && sec + 64 <= fp + d[k].len && (reinterpret_cast<uintptr_t>(chk) & 63) != 63;
-      mine[k] = whole[k] ? sec + 16 * (t & 3) : chk;
-      o[k] = static_cast<int>(chk - mine[k]);
-      if (whole[k]) v[k] = load_nt(reinterpret_cast<const uint4 *>(mine[k]));   // plain: 296 -> 311 us
-    }
-#pragma unroll
-    for (int k = 0; k < kScatterU; ++k) {
-      const uint32_t t = t0 + k * nthreads;
-      const uint16_t c = static_cast<uint16_t>(r[k]);
-      if (whole[k]) {
-        uint4 w = put_byte(v[k], o[k], c);
-        w = put_byte(w, o[k] + 1, c >> 8);
-        store_nt16(mine[k], w);
-      } else if (rec[k] && (t & 3) == 0) {
-        XSKNF_GST(mine[k], 2) {
-          mine[k][0] = static_cast<uint8_t>(c);
-          mine[k][1] = static_cast<uint8_t>(c >> 8);
-        }
-      }
-      if (rec[k] && (t & 3) == 0) {
-        XSKNF_GST(args.verdicts + (t >> 2), 4) args.verdicts[t >> 2] = args.fwd_verdict;
-      }
-    }
-  }
-}
-
-// Sparse records: one lane per frame scans; each wave ballots its 64 frames and
-// rewrites only its records, 16 per round (4 lanes each), so the pass costs in
-// proportion to the records (IMIX: 1 frame in 12), not to n.
-__device__ __forceinline__ void scatter_sparse(const KernelArgs &args, uint8_t *which) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-  const uint32_t waves = gridDim.x * kWavesPerBlock;
-  for (uint32_t base = (blockIdx.x * kWavesPerBlock + wv) * kWave; base < args.n; base += waves * kWave) {
-    const uint32_t f = base + lane;
-    const uint32_t r = f < args.n ? static_cast<uint32_t>(*XSKNF_GLD(args.verdicts + f, 4)) : 0u;
-    const bool rec = (r & kRecTagMask) == kRecTag;
-    const uint64_t m = __builtin_amdgcn_ballot_w64(rec);
-    if (!m) continue;
-    const int nrec = __builtin_popcountll(m);
-    if (rec) {
-      const int rank = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32),
-                                                 __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), 0u));
-      which[rank] = static_cast<uint8_t>(lane);
-    }
-    __builtin_amdgcn_wave_barrier();
-    for (int k0 = 0; k0 < nrec; k0 += kWave / 4) {
-      const int k = k0 + (lane >> 2);
-      const int src = which[min(k, nrec - 1)];
-      const uint32_t rs = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(src << 2, static_cast<int>(r)));
-      if (k < nrec) rewrite_check(args, base + src, rs, *XSKNF_GLD(args.descs + base + src, 16), lane & 3);
-    }
-    __builtin_amdgcn_wave_barrier();   // `which` is rewritten by the next chunk
-  }
-}
-
-__global__ __launch_bounds__(kBlock) void scatter_checks(const KernelArgs args) {
-  __shared__ uint8_t which[kWavesPerBlock][kWave];     // record rank -> lane (sparse shape)
-  // nothing parked: done (exact, see g_rec_count); an unknown count (the
-  // counter set was reused by a later launch in flight) takes the sparse scan,
-  // which finds any record
-  const uint32_t cnt = __builtin_amdgcn_readfirstlane(launch_records(args));
-  if (cnt == 0) return;
-  if (cnt != kCountUnknown && 4ull * cnt >= args.n)
-    scatter_dense(args);
-  else
-    scatter_sparse(args, which[threadIdx.x / kWave]);
-}
-
-// ---- the resident worker (checksummer_internal.h) ------------------------------
-//
-// ONE kernel per device serves every RESIDENT context's ring (ResLaunch::ring).
-// ResLaunch::block maps each block to its ring, its place g in an entry's group
-// and its first entry; a block serves entries b, b + kResSlots / E, ... of that
-// ring (E = ResArgs::entries_per_block, 1 unless the rings would need more
-// blocks than the grid may have).  Its first lane polls those entries' headers
-// (in host memory, or in device memory the host writes through the BAR) for
-// the next sequence number that maps to each, which carries the batch's frame
-// count in the same word: system-scope RELAXED loads (vector loads that bypass
-// the caches without the invalidation an acquire adds per poll), all E of them
-// issued before any is compared; the acquire is one fence once a batch with
-// frames for this block is there.  The blocks of a group deal the batch in
-// 64-frame rounds (the register kernel's tiles, 8 lanes x 12 chunks per frame:
-// a frame of up to 1536 B in one pass, longer ones in further passes), so a
-// 256-frame batch is one round of PCIe reads on each of four CUs and a 64-frame
-// batch one round on one; each block with frames stores its `done` to host
-// memory (system-scope release).  A ring whose batches are at most 64 frames
-// runs one block per entry (ResRing::group = 1): idle blocks' polls cost those
-// batches ~1 us.  A block without frames reads nothing but the word and moves
-// on; it may find the entry already past it (the host waits only for the
-// blocks with frames), and then takes the newer number.
-// A block leaves when the host sets the stop word (a ring joins or leaves), when
-// NO block has finished a batch for idle_ticks (ResLaunch::act, the clock of
-// the latest batch, kept by an atomic max at most every idle_ticks / 8 per
-// block), or after life_ticks in all; it
-// tells the others by setting act to kResQuit, and the last block to leave
-// reports the launch's epoch in ctl->exited.  A batch published to a kernel
-// that has left waits for the host to relaunch it (every block then starts at
-// its entries' first batch not done).  Every wave reaches an exit: the poll
-// loops are bounded by the clock, and a batch is a bounded loop.
-constexpr int kResLpf = 8, kResNch = 12, kResSpt = 2;
-
-// A wave-uniform value read from LDS, moved to scalar registers: addresses
-// built from it then use the SGPR-base forms, as with kernel arguments.
-__device__ __forceinline__ uint32_t uniform_u32(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ uint64_t uniform_u64(uint64_t v) {
-  return static_cast<uint64_t>(uniform_u32(static_cast<uint32_t>(v >> 32))) << 32 | uniform_u32(static_cast<uint32_t>(v));
-}
-// ... and known to address global memory: a pointer read from LDS is generic,
-// and every access through it would be a FLAT instruction (both counters, no
-// scalar base); made from the integer as a global pointer, then cast to
-// generic, its uses get the GLOBAL forms from the compiler's address-space
-// inference, as kernel arguments do.
-template <typename T>
-__device__ __forceinline__ T *uniform_ptr(T *p) {
-  typedef __attribute__((address_space(1))) T gT;
-  gT *const q = (gT *)uniform_u64(reinterpret_cast<uint64_t>(p));   // an integer made a global pointer ...
-  return (T *)q;                                                     // ... then generic: inferable
-}
-
-__global__ __launch_bounds__(kBlock) void resident_kernel(const ResArgs ra) {
-  static_assert(kResBlockFrames == kWavesPerBlock * kResSpt * (kWave / kResLpf), "one round per block");
-  __shared__ uint64_t cmd;
-  __shared__ uint32_t hdr[5];
-  // the block's ring, read once into scalar registers: the system-scope
-  // acquire of every batch invalidates the caches, and the ring's pointers
-  // would be re-read from memory behind it on each batch's critical path
-  // (read through ra.rings, a read-only view: the compiler then knows them to
-  // be global pointers and uses the GLOBAL forms, not FLAT)
-  ResLaunch *const L = ra.L;
-  const uint32_t m = L->block[blockIdx.x];
-  const uint32_t r = m >> 16, g = (m >> 8) & 0xff, b0 = m & 0xff;
-  const ResRing &Rg = ra.rings[r];
-  uint8_t *const r_umem = uniform_ptr(Rg.umem);
-  const uint64_t r_umem_size = uniform_u64(Rg.umem_size);
-  ResIn *const in = uniform_ptr(Rg.in);
-  xsknf_gpu_desc *const r_descs = uniform_ptr(Rg.descs);
-  ResOut *const r_out = uniform_ptr(Rg.out);
-  int32_t *const r_verdicts = uniform_ptr(Rg.verdicts);
-  const uint32_t G = uniform_u32(Rg.group);
-  const uint32_t E = ra.entries_per_block, stride = kResSlots / E;
-  // lane 0's state: the next sequence number of each entry it serves (in LDS:
-  // registers live across group_tiles would cost the kernel its second wave per SIMD)
-  __shared__ uint64_t next[kResSlots];
-  if (threadIdx.x < kResSlots)
-    next[threadIdx.x] = threadIdx.x < E ? L->start[r][(b0 + threadIdx.x * stride) * kResGroup + g] : kResQuit;
-  __syncthreads();
-  const uint64_t t0 = wall_clock64();
-  uint64_t last = t0, told = t0;   // this block's latest batch; when it last told L->act
-  for (;;) {
-    if (threadIdx.x == 0) {
-      uint64_t c = kResQuit;
-      uint32_t n = 0, b = b0;
-      for (bool got = false; !got;) {
-        // every word of the poll issued before any is looked at: one round
-        // trip per poll, not one per word
-        uint64_t w[kResSlots];
-#pragma unroll
-        for (uint32_t j = 0; j < kResSlots; ++j)
-          w[j] = j < E ? __hip_atomic_load(&in[b0 + j * stride].seqn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)
-                       : 0;
-        const uint64_t act = __hip_atomic_load(&L->act, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const uint64_t stop = __hip_atomic_load(ra.stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        const uint64_t now = wall_clock64();
-#pragma unroll
-        for (uint32_t j = 0; j < kResSlots; ++j) {
-          // a number past next[j]: the entry moved on while this block had no
-          // frames in its batches (the host waits for the blocks that do)
-          if (!got && j < E && (w[j] >> 16) >= next[j]) {
-            got = true;
-            c = w[j] >> 16;
-            n = static_cast<uint32_t>(w[j] & 0xFFFF);
-            b = b0 + j * stride;
-            next[j] = c + kResSlots;
-          }
-        }
-        if (got) break;
-        // (a signed difference: another block's latest batch may have ended
-        // after this block read the clock)
-        const int64_t idle = static_cast<int64_t>(now - (act > last ? act : last));
-        if ((act == kResQuit) | (stop != 0) | (idle > static_cast<int64_t>(ra.idle_ticks)) |
-            (now - t0 > ra.life_ticks)) {
-          __hip_atomic_fetch_max(&L->act, kResQuit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          break;
-        }
-        __builtin_amdgcn_s_sleep(2);
-      }
-      if (c != kResQuit) {
-        // (the header is read only by a block with frames: the host cannot
-        // rewrite it before that block's done; a block without frames skips
-        // the fence, whose cache invalidation would cost the XCD's busy blocks)
-        hdr[3] = g < res_used_blocks(n, G);
-        hdr[0] = hdr[3] ? n : 0;
-        hdr[4] = b;
-        if (hdr[3]) {
-          // the host's writes of this batch (header, descriptors, frames), seen from this CU
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");   // system scope
-          // fwd and payload_mult in one 8-byte load (one round trip)
-          const uint64_t fm = __hip_atomic_load(reinterpret_cast<uint64_t *>(&in[b].fwd), __ATOMIC_RELAXED,
-                                                __HIP_MEMORY_SCOPE_SYSTEM);
-          hdr[1] = static_cast<uint32_t>(fm);
-          hdr[2] = static_cast<uint32_t>(fm >> 32);
-        }
-      }
-      cmd = c;
-    }
-    __syncthreads();
-    const uint64_t c = cmd;
-    if (c == kResQuit) break;
-    {
-      const uint32_t b = uniform_u32(hdr[4]);
-      // the ring's UMEM is host memory mapped over PCIe: every check in-line as
-      // a 2-byte store (byte enables, no read-modify-write); the store modes are
-      // constants here, so only the ring's pointers take (scalar) registers
-      KernelArgs a;
-      a.umem = r_umem;
-      a.umem_size = r_umem_size;
-      a.descs = r_descs + static_cast<size_t>(b) * kResFrames;
-      a.verdicts = r_verdicts + static_cast<size_t>(b) * kResFrames;
-      a.dummy = reinterpret_cast<const uint4 *>(r_descs);
-      a.n = min(uniform_u32(hdr[0]), kResFrames);
-      a.fwd_verdict = static_cast<int32_t>(uniform_u32(hdr[1]));
-      a.payload_mult = uniform_u32(hdr[2]);
-      a.defer_min_len = kNoDefer;
-      a.no_scatter = 0;
-      a.seq = 0;
-      a.count_records = 0;
-      a.sector_stores = 0;
-      a.plain_sector = 0;
-      a.tail_scatter = 0;
-      a.store_unchanged = 0;
-      // the group's blocks deal the batch in 64-frame rounds: block g takes
-      // frames [64 g, 64 g + 64) of a batch of up to 256
-      if (a.n) group_tiles<kResLpf, kResNch, kResSpt>(a, g, G);
-      __syncthreads();   // the block's stores are done (workgroup release / acquire)
-      if (threadIdx.x == 0) {
-        if (hdr[3]) {
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");   // system scope: the checks and verdicts
-          __hip_atomic_store(&r_out[b * kResGroup + g].done, c, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-        last = wall_clock64();
-        // the device-wide activity only needs the idle exit's precision: an
-        // atomic per batch (on one word, from every block) would sit in front
-        // of the next poll's wait
-        if (last - told > ra.idle_ticks / 8) {
-          __hip_atomic_fetch_max(&L->act, last, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          told = last;
-        }
-      }
-    }
-  }
-  if (threadIdx.x == 0 &&
-      __hip_atomic_fetch_add(&L->exits, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == ra.blocks - 1)
-    __hip_atomic_store(&ra.ctl->exited, ra.epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
+#include "csum_device.h"
+#include "kernel_group.h"
+#include "kernel_lane.h"
+#include "kernel_split.h"
+#include "kernel_scatter.h"
+#include "kernel_resident.h"
 
 // ---- host side ----------------------------------------------------------------
-
-}  // namespace xsknf_gpu
 
 // A/B builds (make ab) add launch shapes and knobs; the product sees no-ops
 #ifdef XSKNF_AB
@@ -2226,17 +265,28 @@ int launch_reg(const KernelArgs &a, hipStream_t stream, int blocks_per_cu) {
   return finish_launch(a, stream, "checksum_kernel launch");
 }
 
+// Whether the device can make one block of `threads` threads of `kernel`
+// resident (a block holding a whole CU's waves and ~160 KiB of LDS may not
+// fit): asked once per thread and kernel.
+bool block_fits(const void *kernel, int threads) {
+  struct Entry { const void *k; bool fits; };
+  static thread_local Entry cache[16];
+  static thread_local int used = 0;
+  for (int i = 0; i < used; ++i)
+    if (cache[i].k == kernel) return cache[i].fits;
+  int b = 0;
+  const bool fits = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, kernel, threads, 0) == hipSuccess && b > 0;
+  (void)hipGetLastError();
+  if (used < 16) cache[used++] = Entry{kernel, fits};
+  return fits;
+}
+
 template <int NCH, int SPT, int SW = kWavesPerBlock, int WPE = 1, int TLM = 0>
 int launch_lane(const KernelArgs &a, hipStream_t stream, int blocks_per_cu) {
   auto k = checksum_kernel_lane<NCH, SPT, SW, WPE, TLM>;
   if constexpr (SW > kWavesPerBlock) {   // as launch_split: a CU-sized block the device cannot hold
-    static thread_local int fits = -1;
-    if (fits < 0) {
-      int b = 0;
-      fits = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k, SW * kWave, 0) == hipSuccess && b > 0;
-      (void)hipGetLastError();
-    }
-    if (!fits) return launch_lane<NCH, SPT, kWavesPerBlock>(a, stream, blocks_per_cu);
+    if (!block_fits(reinterpret_cast<const void *>(k), SW * kWave))
+      return launch_lane<NCH, SPT, kWavesPerBlock>(a, stream, blocks_per_cu);
   }
   hipLaunchKernelGGL(k, dim3(grid_blocks(k, a.n, blocks_per_cu, SPT * kWave, SW)), dim3(SW * kWave), 0, stream, a);
   return finish_launch(a, stream, "checksum_kernel_lane launch");
@@ -2248,13 +298,8 @@ int launch_split(const KernelArgs &a, hipStream_t stream, int blocks_per_cu) {
   if constexpr (SW > kWavesPerBlock) {
     // a block holding a whole CU's waves (and ~160 KiB of LDS) that the device
     // cannot make resident runs as the 4-wave shape with the static schedule
-    static thread_local int fits = -1;
-    if (fits < 0) {
-      int b = 0;
-      fits = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k, SW * kWave, 0) == hipSuccess && b > 0;
-      (void)hipGetLastError();
-    }
-    if (!fits) return launch_split<W, LPF, NCH, U, TL, kWavesPerBlock>(a, stream, blocks_per_cu);
+    if (!block_fits(reinterpret_cast<const void *>(k), SW * kWave))
+      return launch_split<W, LPF, NCH, U, TL, kWavesPerBlock>(a, stream, blocks_per_cu);
   }
   uint32_t grid = grid_blocks(k, a.n, blocks_per_cu, kWave, SW);
   constexpr uint32_t PT = patch_list_tiles<W, NCH, U, pooled_split(SW)>();
@@ -2288,24 +333,26 @@ int launch_split(const KernelArgs &a, hipStream_t stream, int blocks_per_cu) {
 
 // Instantiated launch shapes: {lanes per frame, 16-B chunks per lane and pass,
 // frames per group and step (register) / items per group in flight (split),
-// LDS ring slots (always 0: the LDS-DMA kernels were A/B material, removed in
-// round 5), kernel family, header window chunks}.
+// kernel family, window field (header window chunks + the kWin flags)}.
 struct Variant {
-  int lpf, nch, u, ring;
+  int lpf, nch, u;
   int (*fn)(const KernelArgs &, hipStream_t, int);
   int kernel = XSKNF_GPU_KERNEL_AUTO, window = 0;
 };
 
-#define XSKNF_V(L, N, S) {L, N, S, 0, &launch_reg<L, N, S>}
-#define XSKNF_L(N, S) {1, N, S, 0, &launch_lane<N, S>}
-// ... transposed per tile where the tile's frames lie apart (window field 1024)
-#define XSKNF_LA(N, S) {1, N, S, 0, &launch_lane<N, S, kWavesPerBlock, 4, 2>, XSKNF_GPU_KERNEL_AUTO, 1024}
-// split: window field = W, + 16 for the transposed (coalesced) window load
-#define XSKNF_S(W, L, N, U, TL) {L, N, U, 0, &launch_split<W, L, N, U, TL>, XSKNF_GPU_KERNEL_SPLIT, W + 16 * TL}
-// one 12-wave block per CU, its waves drawing the CU's tiles from a shared pool (window field + 32)
-#define XSKNF_SC(L, N, U) {L, N, U, 0, &launch_split<8, L, N, U, true, 12>, XSKNF_GPU_KERNEL_SPLIT, 56}
+#define XSKNF_V(L, N, S) {L, N, S, &launch_reg<L, N, S>}
+#define XSKNF_L(N, S) {1, N, S, &launch_lane<N, S>}
+// ... transposed per tile where the tile's frames lie apart
+#define XSKNF_LA(N, S) {1, N, S, &launch_lane<N, S, kWavesPerBlock, 4, 2>, XSKNF_GPU_KERNEL_AUTO, kWinLanePerTile}
+// split: window field = W, + kWinTransposed for the transposed (coalesced) window load
+#define XSKNF_S(W, L, N, U, TL) \
+  {L, N, U, &launch_split<W, L, N, U, TL>, XSKNF_GPU_KERNEL_SPLIT, W + kWinTransposed * TL}
+// one 12-wave block per CU, its waves drawing the CU's tiles from a shared pool (+ kWinPool)
+#define XSKNF_SC(L, N, U) \
+  {L, N, U, &launch_split<8, L, N, U, true, 12>, XSKNF_GPU_KERNEL_SPLIT, 8 + kWinTransposed + kWinPool}
 // jumbo: one 8-wave block per CU (174 VGPRs: 2 waves per SIMD), W = 4
-#define XSKNF_SC4(L, N, U) {L, N, U, 0, &launch_split<4, L, N, U, true, 8>, XSKNF_GPU_KERNEL_SPLIT, 52}
+#define XSKNF_SC4(L, N, U) \
+  {L, N, U, &launch_split<4, L, N, U, true, 8>, XSKNF_GPU_KERNEL_SPLIT, 4 + kWinTransposed + kWinPool}
 const Variant kVariants[] = {
     // the product's shapes: default_cfg()'s split kernels, one per size class ...
     XSKNF_S(4, 16, 2, 2, 1), XSKNF_S(8, 16, 2, 2, 1), XSKNF_SC(16, 2, 2), XSKNF_S(8, 16, 3, 1, 1),
@@ -2319,11 +366,7 @@ const Variant kVariants[] = {
 };
 #undef XSKNF_V
 #undef XSKNF_L
-#undef XSKNF_LP
-#undef XSKNF_LT
 #undef XSKNF_LA
-#undef XSKNF_LW
-#undef XSKNF_LPA
 #undef XSKNF_S
 #undef XSKNF_SC
 #undef XSKNF_SC4
@@ -2333,10 +376,10 @@ const Variant *find_variant(const xsknf_gpu_launch_cfg &c) {
     if (v.kernel != c.kernel) continue;
     if (v.kernel == XSKNF_GPU_KERNEL_SPLIT) {
       if (v.lpf == c.lanes_per_frame && v.nch == c.chunks_per_lane && v.u == c.frames_per_group &&
-          v.window == c.window_chunks && v.ring == c.lds_ring)
+          v.window == c.window_chunks)
         return &v;
-    } else if (v.lpf == c.lanes_per_frame && v.nch == c.chunks_per_lane && v.ring == c.lds_ring &&
-               v.u == c.frames_per_group && v.window == (c.window_chunks & ~31)) {
+    } else if (v.lpf == c.lanes_per_frame && v.nch == c.chunks_per_lane &&
+               v.u == c.frames_per_group && v.window == (c.window_chunks & ~(kWinPool - 1))) {
       return &v;
     }
   }
@@ -2386,18 +429,20 @@ void default_cfg(uint32_t hint, xsknf_gpu_launch_cfg &c, uint32_t mean) {
   c.lanes_per_frame = 16;
   if (hint <= 128) {
     c.kernel = XSKNF_GPU_KERNEL_AUTO;
-    // (+ 1024: windows loaded transposed where a tile's frames lie apart; 3
+    // (+ kWinLanePerTile: windows loaded transposed where a tile's frames lie apart; 3
     // blocks per CU of the 4 that fit: 64 B 56.7-57.1 vs 56.8-57.2 us, packed
     // 64 B NIC 20.2-20.3 vs 22.5-22.8, nothing slower -- ab_lane_bpc_r05z.jsonl)
-    c.lanes_per_frame = 1; c.window_chunks = 1024; c.chunks_per_lane = 5; c.frames_per_group = 2; c.fused_stores = 1;
+    c.lanes_per_frame = 1; c.window_chunks = kWinLanePerTile; c.chunks_per_lane = 5; c.frames_per_group = 2;
+    c.fused_stores = kStoreInline;
     c.blocks_per_cu = 3;
   } else if (hint + 15 <= 4096) {
     // the CU-wide tile pool (+ 32) but for a known mix of mostly short frames
     // (IMIX: 115.9 vs 114.3 us with 4-wave blocks and the static schedule)
-    c.window_chunks = 8 + 16 + (mean != 0 && mean < kPoolMinMean ? 0 : 32);
-    c.chunks_per_lane = 2; c.frames_per_group = 2; c.fused_stores = 2 + 16;
+    c.window_chunks = 8 + kWinTransposed + (mean != 0 && mean < kPoolMinMean ? 0 : kWinPool);
+    c.chunks_per_lane = 2; c.frames_per_group = 2; c.fused_stores = kStoreDeferred + kStoreTailPatch;
   } else {
-    c.window_chunks = 4 + 16 + 32; c.chunks_per_lane = 3; c.frames_per_group = 2; c.fused_stores = 2 + 16;
+    c.window_chunks = 4 + kWinTransposed + kWinPool; c.chunks_per_lane = 3; c.frames_per_group = 2;
+    c.fused_stores = kStoreDeferred + kStoreTailPatch;
   }
 }
 
@@ -2434,26 +479,31 @@ constexpr uint32_t kLaunchFrames = 1u << 20;
 constexpr uint32_t kLaneLaunchFrames = 1u << 24;
 constexpr uint32_t kLaneTransposedMaxFrames = 2u << 20;
 
+// cfg.fused_stores (the kStore constants) as the kernels' flags: which checks are
+// deferred, and who writes the deferred ones -- the split kernel's own patches,
+// the scatter pass (which then needs the records counted), or the caller.
+void set_store_mode(KernelArgs &a, int fused_stores, bool split_kernel) {
+  const int mode = fused_stores & kStoreModeMask;
+  a.defer_min_len = mode == kStoreInline ? kNoDefer : (mode == kStorePerTile ? kDeferMinLen : 0u);
+  if (mode == kStoreRecordsOnly) a.no_scatter = 1;
+  if (fused_stores & kStoreTwoByte) a.sector_stores = 0;
+  if (fused_stores & kStorePlainSector) a.plain_sector = 1;
+  if (fused_stores & kStoreUnchanged) a.store_unchanged = 1;
+  const bool deferred_here = a.defer_min_len != kNoDefer && !a.no_scatter;
+  // (the patch list indexes 64-byte sectors in 32 bits: a larger UMEM parks its
+  // checks for the scatter pass instead)
+  a.tail_scatter = deferred_here && (fused_stores & kStoreTailPatch) && split_kernel && a.umem_size < kPatchMaxUmem;
+  a.count_records = deferred_here && !a.tail_scatter;
+}
+
 int run(const KernelArgs &base, const xsknf_gpu_launch_cfg &cfg, void *stream, bool product_shape) {
   if (cfg.blocks_per_cu < 0 || cfg.blocks_per_cu > 64) return -EINVAL;
-  // + 4: 2-byte in-line stores, + 8: plain sector stores, + 32: write unchanged checks too
-  const int mode = cfg.fused_stores & 3;
-  if (cfg.fused_stores < 0 || cfg.fused_stores > 63) return -EINVAL;
+  if (cfg.fused_stores < 0 || cfg.fused_stores > kStoreAllBits) return -EINVAL;
+  if (cfg.lds_ring != 0) return -EINVAL;   // (the LDS-DMA kernels it selected were removed in round 5)
   const Variant *v = find_variant(cfg);
   if (!v) return -EINVAL;
   KernelArgs a = base;
-  a.defer_min_len = mode == 1 ? kNoDefer : (mode >= 2 ? 0u : kDeferMinLen);
-  if (mode == 3) a.no_scatter = 1;   // records only: the caller applies the checks
-  if (cfg.fused_stores & 4) a.sector_stores = 0;
-  if (cfg.fused_stores & 8) a.plain_sector = 1;
-  if (cfg.fused_stores & 32) a.store_unchanged = 1;
-  // + 16: the split kernel patches its deferred checks itself (no scatter launch)
-  a.tail_scatter = (cfg.fused_stores & 16) && v->kernel == XSKNF_GPU_KERNEL_SPLIT && a.defer_min_len != kNoDefer &&
-                   !a.no_scatter;
-  // the patch list indexes 64-byte sectors in 32 bits: a larger UMEM parks its
-  // checks for the scatter pass instead
-  if (a.umem_size >= kPatchMaxUmem) a.tail_scatter = 0;
-  a.count_records = a.defer_min_len != kNoDefer && !a.no_scatter && !a.tail_scatter;
+  set_store_mode(a, cfg.fused_stores, v->kernel == XSKNF_GPU_KERNEL_SPLIT);
   // A batch larger than kLaunchFrames runs as consecutive launches of that many
   // frames: one launch over the whole of an 8M-frame IMIX batch (config 4 on
   // one GPU, 16 GB of UMEM) takes 133 us per 1M frames against 113 for 1M-frame
@@ -2465,7 +515,7 @@ int run(const KernelArgs &base, const xsknf_gpu_launch_cfg &cfg, void *stream, b
   // 50.2 us per 1M frames in one launch against 58.6 in 13 launches, 4M 55.4
   // against 57.9 (profiles/r05/ab/ab_lane_launch_frames.jsonl).
   const uint32_t lf = v->lpf == 1 && v->kernel != XSKNF_GPU_KERNEL_SPLIT ? kLaneLaunchFrames : kLaunchFrames;
-  // The lane kernel's per-tile transposed windows (window field 1024) pay off
+  // The lane kernel's per-tile transposed windows (kWinLanePerTile) pay off
   // in a launch of up to a few M frames, per-lane loads in a longer one (64 B,
   // profiles/r05/ab/ab_lane_la_r05n.jsonl: 1M frames 57.5-57.7 vs 58.3-59.0 us,
   // 13M frames in one launch 701-710 vs 655-662 us): a longer launch runs as
@@ -2473,7 +523,7 @@ int run(const KernelArgs &base, const xsknf_gpu_launch_cfg &cfg, void *stream, b
   // Only for the product's own shape (default_cfg, or an explicit cfg that leaves
   // blocks_per_cu to the library): an explicit shape runs as asked.
   const Variant *longer = v;
-  if (product_shape && v->kernel == XSKNF_GPU_KERNEL_AUTO && v->lpf == 1 && v->window == 1024) {
+  if (product_shape && v->kernel == XSKNF_GPU_KERNEL_AUTO && v->lpf == 1 && v->window == kWinLanePerTile) {
     xsknf_gpu_launch_cfg c = cfg;
     c.window_chunks = 0;
     if (const Variant *w = find_variant(c)) longer = w;

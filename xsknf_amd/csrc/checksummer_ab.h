@@ -1,4 +1,4 @@
-// checksummer_ab.h -- A/B-only launch shapes and knobs of checksummer.hip.
+// checksummer_ab.h -- A/B-only launch shapes and knobs of checksummer.hip's host side.
 //
 // Included only by A/B builds (`make ab` -> build/ab/libxsknf_gpu.so, -DXSKNF_AB;
 // tools/tune.py, tools/ab_*.sh): nothing here is in the product library.  The
@@ -32,15 +32,22 @@ inline bool ab_no_grid_bound() {
 
 }  // namespace xsknf_gpu
 
-// Variant constructors of the A/B-only kernels (checksummer.hip's Variant table)
-// lane kernel, one 16-wave block per CU with the tile pool (window field 32)
-#define XSKNF_LP(N, S) {1, N, S, 0, &launch_lane<N, S, 16>, XSKNF_GPU_KERNEL_AUTO, 32}
-// lane kernel with the transposed (coalesced) window load (window field 512)
-#define XSKNF_LT(N, S) {1, N, S, 0, &launch_lane<N, S, kWavesPerBlock, 1, 1>, XSKNF_GPU_KERNEL_AUTO, 512}
+// Variant constructors of the A/B-only kernels (find_variant's table in
+// checksummer.hip) and their window fields, beside kWinPool / kWinLanePerTile
+namespace xsknf_gpu {
+constexpr int kWinLaneTransposed = 512;   // lane kernel: every window loaded transposed
+constexpr int kWinLaneWaves = 64;         // lane kernel held to WPE waves per SIMD: + kWinLaneWavesStep * WPE
+constexpr int kWinLaneWavesStep = 256;
+}  // namespace xsknf_gpu
+// lane kernel, one 16-wave block per CU with the tile pool
+#define XSKNF_LP(N, S) {1, N, S, &launch_lane<N, S, 16>, XSKNF_GPU_KERNEL_AUTO, kWinPool}
+// lane kernel with the transposed (coalesced) window load
+#define XSKNF_LT(N, S) {1, N, S, &launch_lane<N, S, kWavesPerBlock, 1, 1>, XSKNF_GPU_KERNEL_AUTO, kWinLaneTransposed}
 // (A/B) the pooled lane kernel with the per-tile transposed windows (window field 1056)
-#define XSKNF_LPA(N, S) {1, N, S, 0, &launch_lane<N, S, 16, 4, 2>, XSKNF_GPU_KERNEL_AUTO, 1056}
-// (A/B) lane kernel held to WPE waves per SIMD (window field 64 + 256 * WPE)
-#define XSKNF_LW(N, S, WPE) {1, N, S, 0, &launch_lane<N, S, kWavesPerBlock, WPE>, XSKNF_GPU_KERNEL_AUTO, 64 + 256 * WPE}
+#define XSKNF_LPA(N, S) {1, N, S, &launch_lane<N, S, 16, 4, 2>, XSKNF_GPU_KERNEL_AUTO, kWinLanePerTile + kWinPool}
+// (A/B) lane kernel held to WPE waves per SIMD
+#define XSKNF_LW(N, S, WPE) \
+  {1, N, S, &launch_lane<N, S, kWavesPerBlock, WPE>, XSKNF_GPU_KERNEL_AUTO, kWinLaneWaves + kWinLaneWavesStep * WPE}
 
 // A/B material, appended to the product's Variant table
 #define XSKNF_AB_VARIANTS \

@@ -1,10 +1,12 @@
 // checksummer_internal.h -- declarations shared by the gfx950 checksummer
-// kernels (checksummer.hip) and the host-path context (host_path.hip).
+// kernels (csum_device.h, kernel_*.h), their host side (checksummer.hip), the
+// host-path context (host_path.hip) and the multi-device calls (multi.hip).
 // Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/xsknf.h"   // XSKNF_MAX_INTERFACES
 #include "../../include/xsknf_gpu.h"
 
 namespace xsknf_gpu {
@@ -38,9 +40,51 @@ struct KernelArgs {
 // Check record parked in verdicts[f] by the summing pass (deferred stores):
 // tag 01 in bits 31..30 (no verdict, -1 or 0..XSKNF_MAX_INTERFACES-1, has it),
 // u in bits 22..16, the new check in bits 15..0.
+// The bit layout is known only to these helpers (host and device).
 constexpr uint32_t kRecTag = XSKNF_GPU_RECORD_TAG;
 constexpr uint32_t kRecTagMask = XSKNF_GPU_RECORD_TAG_MASK;
+__host__ __device__ constexpr uint32_t make_record(uint32_t u, uint16_t c) { return kRecTag | (u << 16) | c; }
+__host__ __device__ constexpr bool is_record(uint32_t word) { return (word & kRecTagMask) == kRecTag; }
+// the check's offset in its frame (u + 6) and its value (low byte first in the frame)
+__host__ __device__ constexpr uint32_t record_check_offset(uint32_t word) { return ((word >> 16) & 0x7f) + 6; }
+__host__ __device__ constexpr uint16_t record_check(uint32_t word) { return static_cast<uint16_t>(word); }
+// The register kernel's PENDING word (a frame longer than one pass, in the
+// tile's LDS results only: step_result / finish_long_frames): tag 10, u below.
+constexpr uint32_t kPendTag = 0x80000000u;
+__host__ __device__ constexpr uint32_t make_pending(uint32_t u) { return kPendTag | u; }
+__host__ __device__ constexpr bool is_pending(uint32_t word) { return (word & kRecTagMask) == kPendTag; }
+__host__ __device__ constexpr uint32_t pending_u(uint32_t word) { return word & 0x7f; }
+
+constexpr bool record_round_trip(uint32_t u, uint16_t c) {
+  return is_record(make_record(u, c)) && record_check_offset(make_record(u, c)) == u + 6 &&
+         record_check(make_record(u, c)) == c && !is_pending(make_record(u, c));
+}
+static_assert(record_round_trip(14, 0) && record_round_trip(14, 0xffff) && record_round_trip(74, 0) &&
+                  record_round_trip(74, 0xffff), "u = 14 + 4 * ihl (14..74) and any check survive the record");
+static_assert(!is_record(static_cast<uint32_t>(-1)) && !is_record(0u) && !is_record(XSKNF_MAX_INTERFACES - 1u) &&
+                  !is_pending(static_cast<uint32_t>(-1)) && !is_pending(XSKNF_MAX_INTERFACES - 1u),
+              "no verdict (-1 .. XSKNF_MAX_INTERFACES - 1) reads as a record or a pending word");
+static_assert(kPendTag != kRecTag && (kPendTag & kRecTagMask) == kPendTag && pending_u(make_pending(74)) == 74,
+              "the record and pending tags are distinct");
+
 constexpr uint32_t kNoDefer = 0xffffffffu;   // defer_min_len: every check in-line
+
+// xsknf_gpu_launch_cfg::window_chunks (include/xsknf_gpu.h): the header window's
+// chunks plus these flags ...
+constexpr int kWinTransposed = 16;    // split kernel: transposed (coalesced) window load
+constexpr int kWinPool = 32;          // one block per CU, its waves sharing the CU's tiles
+constexpr int kWinLanePerTile = 1024; // lane kernel: windows transposed where a tile's frames lie apart
+// ... and ::fused_stores: a store mode plus flags
+constexpr int kStoreModeMask = 3;
+constexpr int kStorePerTile = 0;      // long frames defer their checks where they are half of a tile
+constexpr int kStoreInline = 1;       // every check in-line
+constexpr int kStoreDeferred = 2;     // every check deferred
+constexpr int kStoreRecordsOnly = 3;  // deferred and left as records: the caller applies the checks
+constexpr int kStoreTwoByte = 4;      // in-line checks as 2-byte stores, not whole sectors
+constexpr int kStorePlainSector = 8;  // whole-sector stores of the lane kernel plain, not non-temporal
+constexpr int kStoreTailPatch = 16;   // the split kernel patches its deferred checks itself (no scatter launch)
+constexpr int kStoreUnchanged = 32;   // write a check even when the frame already holds it
+constexpr int kStoreAllBits = 63;
 
 // Validate arguments and fill `a` (returns 1 for an empty batch, <0 on error).
 int prepare(KernelArgs &a, uint8_t *umem, uint64_t umem_size, const xsknf_gpu_desc *descs, uint32_t n,

@@ -43,7 +43,7 @@
 //   own bytes).
 //
 // RESIDENT: ZEROCOPY, but no batch launches a kernel: ONE resident kernel per
-//   device (checksummer.hip resident_kernel, host side ResService below) takes
+//   device (kernel_resident.h resident_kernel, host side ResService below) takes
 //   the batches of every RESIDENT context on the device from each context's
 //   ring, in entries of up to kResFrames frames, a group of one or four 4-wave
 //   blocks per entry, so several batches (or the pieces of a larger one) are
@@ -162,7 +162,7 @@ uint64_t umem_offset(uint64_t addr) {
 // ---- RESIDENT: the device's one resident kernel (ResService) --------------------
 //
 // Every RESIDENT context of a device registers its ring here; one kernel on
-// one stream serves them all (checksummer.hip resident_kernel), so the number
+// one stream serves them all (kernel_resident.h resident_kernel), so the number
 // of workers does not multiply hardware queues or kernels.  The table of rings,
 // the block map and each entry's first sequence number go to the device
 // (ResLaunch) before each launch.  Whoever finds the kernel gone (its last
@@ -424,10 +424,10 @@ int complete(xsknf_gpu_ctx *c, Slot &s) {
     // checksummer_user.c:108 on the host: the 2 check bytes of every summed frame
     for (uint32_t i = 0; i < s.n; ++i) {
       const uint32_t r = static_cast<uint32_t>(s.rec[i]);
-      if ((r & kRecTagMask) == kRecTag) {
-        uint8_t *p = c->umem_host + s.offs[i] + ((r >> 16) & 0x7f) + 6;
-        p[0] = static_cast<uint8_t>(r);
-        p[1] = static_cast<uint8_t>(r >> 8);
+      if (is_record(r)) {
+        uint8_t *p = c->umem_host + s.offs[i] + record_check_offset(r);
+        p[0] = static_cast<uint8_t>(record_check(r));
+        p[1] = static_cast<uint8_t>(record_check(r) >> 8);
         s.out[i] = s.fwd;
       } else {
         s.out[i] = static_cast<int32_t>(r);
@@ -659,10 +659,10 @@ int submit_piece(xsknf_gpu_ctx *c, const xsknf_gpu_desc *descs, uint32_t n, uint
   }
   if (mapped) {
     pcie_small_batch_cfg(n, cfg);
-    cfg.fused_stores = 1;   // in place over PCIe, ...
+    cfg.fused_stores = kStoreInline;   // in place over PCIe, ...
     a.sector_stores = 0;    // ... as 2-byte writes (byte enables; no RMW in host memory)
   } else {
-    cfg.fused_stores = 3;   // records only: the checks are applied on the host (complete())
+    cfg.fused_stores = kStoreRecordsOnly;   // the checks are applied on the host (complete())
   }
   s.host_checks = !mapped;
   rc = run(a, cfg, s.stream, true);

@@ -189,17 +189,18 @@ __global__ void __launch_bounds__(256) pack_frames(const uint8_t *umem, uint64_t
 }
 
 // Root: the returned records / verdicts of the whole batch, in place: a record
-// (XSKNF_GPU_RECORD_TAG | u << 16 | check) writes the check's two bytes, low
+// (make_record(u, check), checksummer_internal.h) writes the check's two bytes, low
 // byte first, at the frame's offset u + 6 (checksummer_user.c:108) and becomes
 // the forward verdict (:110-111); any other value is already the verdict.
 __global__ void __launch_bounds__(256) apply_records(uint8_t *umem, const xsknf_gpu_desc *orig, int32_t *verdicts,
                                                      uint64_t n, int32_t fwd) {
   for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += gridDim.x * 256ull) {
     const uint32_t r = static_cast<uint32_t>(verdicts[i]);
-    if ((r & XSKNF_GPU_RECORD_TAG_MASK) != XSKNF_GPU_RECORD_TAG) continue;
-    uint8_t *p = umem + umem_offset(orig[i].addr) + ((r >> 16) & 0x7f) + 6;
-    p[0] = static_cast<uint8_t>(r);
-    p[1] = static_cast<uint8_t>(r >> 8);
+    if (!xsknf_gpu::is_record(r)) continue;
+    uint8_t *p = umem + umem_offset(orig[i].addr) + xsknf_gpu::record_check_offset(r);
+    const uint16_t c = xsknf_gpu::record_check(r);
+    p[0] = static_cast<uint8_t>(c);
+    p[1] = static_cast<uint8_t>(c >> 8);
     verdicts[i] = fwd;
   }
 }
@@ -591,7 +592,7 @@ int xsknf_gpu_multi_return(struct xsknf_gpu_multi *m, uint32_t ingress_ifindex, 
   xsknf_gpu_launch_cfg cfg;
   int rc = xsknf_gpu_launch_cfg_for_lens(frame_len_max, frame_len_mean, &cfg);
   if (rc) return rc;
-  cfg.fused_stores = 3;   // records only: the shard is read, each changed check comes back as a record
+  cfg.fused_stores = xsknf_gpu::kStoreRecordsOnly;   // the shard is read, each changed check comes back as a record
   const double t0 = now_s();
   for (Shard &s : m->sh) {
     const uint64_t frames = s.hi - s.lo;
