@@ -4,7 +4,8 @@ ARCH ?= gfx950
 HIPFLAGS ?= -O3 -std=c++17 -fPIC -Wall -Wno-inline-asm -fvisibility=hidden --offload-arch=$(ARCH) -Iinclude
 LIBDIR := xsknf_amd/lib
 LIB := $(LIBDIR)/libxsknf_gpu.so
-SRCS := xsknf_amd/csrc/checksummer.hip xsknf_amd/csrc/host_path.hip xsknf_amd/csrc/multi.hip xsknf_amd/csrc/shard_plan.cpp
+SRCS := xsknf_amd/csrc/checksummer.hip xsknf_amd/csrc/host_path.hip xsknf_amd/csrc/multi.hip xsknf_amd/csrc/plan_device.hip \
+	xsknf_amd/csrc/shard_plan.cpp
 # every header the device code may include: checksummer.hip is one translation
 # unit over csum_device.h and the kernel_*.h families
 GPUHDRS := include/xsknf_gpu.h include/xsknf.h $(wildcard xsknf_amd/csrc/*.h)

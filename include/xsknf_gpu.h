@@ -419,6 +419,59 @@ XSKNF_GPU_API int xsknf_gpu_multi_scatter_packed(struct xsknf_gpu_multi *m, int 
 XSKNF_GPU_API int xsknf_gpu_multi_return(struct xsknf_gpu_multi *m, uint32_t ingress_ifindex,
 		const struct xsknf_csum_opts *opts, uint32_t frame_len_max, uint32_t frame_len_mean, uint8_t *umem,
 		int32_t *verdicts, float *ms, double *seconds);
+/* ---- the plan computed on the root device ----
+ * For a batch whose descriptors already lie in the root's device memory (next
+ * to its UMEM): the cuts, spans / packed layout and byte sums above, computed
+ * by kernels on that device instead of one CPU thread, bit-identical to
+ * xsknf_gpu_shard_plan, _shard_rebase and _shard_pack_plan for every input.
+ * The per-frame outputs stay on the device; the host reads back one small
+ * array (the cuts, the spans or sizes, the byte sums). */
+#define XSKNF_GPU_PLAN_SPAN 0     /* spans + rebased descriptors (xsknf_gpu_multi_scatter's plan) */
+#define XSKNF_GPU_PLAN_PACKED 1   /* sizes + packed descriptors (xsknf_gpu_multi_scatter_packed's plan) */
+/* *bytes = the device workspace xsknf_gpu_shard_plan_dev needs for n descriptors
+ * (positive, non-decreasing in n, the same for every nshards in 1..64).  Host
+ * arithmetic; no GPU call.  -EINVAL for nshards 0 or > 64 or a NULL bytes. */
+XSKNF_GPU_API int xsknf_gpu_shard_plan_dev_workspace(uint64_t n, uint32_t nshards, uint64_t *bytes);
+/* Plan n descriptors at `descs` (memory of the current device, 16-byte aligned)
+ * of a UMEM at device address umem_addr into 1 <= nshards <= 64 shards, on
+ * `stream` (a hipStream_t; NULL: the default stream):
+ *   bounds[nshards + 1]   the cuts of xsknf_gpu_shard_plan;
+ *   frame_bytes[nshards]  each shard's sum of frame lengths (may be NULL);
+ *   XSKNF_GPU_PLAN_SPAN:   spans_or_sizes[2 * nshards] = the spans of
+ *     xsknf_gpu_shard_plan, out_descs[f] = frame f's descriptor relative to its
+ *     shard's span (xsknf_gpu_shard_rebase per shard);
+ *   XSKNF_GPU_PLAN_PACKED: spans_or_sizes[nshards] = the sizes and out_descs the
+ *     packed descriptors of xsknf_gpu_shard_pack_plan (umem_addr gives the
+ *     frames' addresses mod 16).
+ * bounds, spans_or_sizes (may be NULL) and frame_bytes are host arrays, filled
+ * when the call returns (it waits for `stream`); out_descs (n records, 16-byte
+ * aligned, not overlapping descs) and workspace (workspace_bytes >= what
+ * _workspace reports, 8-byte aligned) are device memory.  n == 0 succeeds
+ * without a launch (all outputs 0).  -EINVAL, before any GPU call, for nshards
+ * 0 or > 64, a NULL bounds, an unknown mode, and with n > 0 a NULL or
+ * misaligned descs / out_descs / workspace or a workspace too small.  The cut
+ * rule compares in double exactly as the host does (running sums below 2^53
+ * bytes are exact there). */
+XSKNF_GPU_API int xsknf_gpu_shard_plan_dev(const struct xsknf_gpu_desc *descs, uint64_t n, uint64_t umem_addr,
+		uint64_t umem_size, uint32_t nshards, int mode, struct xsknf_gpu_desc *out_descs, uint64_t *bounds,
+		uint64_t *spans_or_sizes, uint64_t *frame_bytes, void *workspace, uint64_t workspace_bytes,
+		void *stream);
+/* xsknf_gpu_multi_scatter (mode XSKNF_GPU_PLAN_SPAN) or _scatter_packed
+ * (XSKNF_GPU_PLAN_PACKED) for descriptors in DEVICE memory: descs_dev (n
+ * records, 16-byte aligned) lies on devices[root] like `umem`.  The plan is
+ * computed there by xsknf_gpu_shard_plan_dev's kernels (the workspace is kept
+ * in the object), the descriptors are kept for _return by a device-to-device
+ * copy (the caller may reuse its buffer once the call returns), and the shards
+ * move exactly as from the host variants: afterwards the object is in the state
+ * the host variant leaves for the same batch, for _process, _counters, _return,
+ * _shard_info and _fetch alike.
+ * *seconds (may be NULL): from the first planning step to the end of the moves
+ * (root and shard buffer allocation included; the host variants' `seconds`
+ * start after their planning and staging).  *plan_seconds (may be NULL): the
+ * planning kernels and the read-back of their result alone. */
+XSKNF_GPU_API int xsknf_gpu_multi_scatter_dev(struct xsknf_gpu_multi *m, int root, const uint8_t *umem,
+		uint64_t umem_size, const struct xsknf_gpu_desc *descs_dev, uint64_t n, int mode, double *seconds,
+		double *plan_seconds);
 XSKNF_GPU_API int xsknf_gpu_multi_shard_info(const struct xsknf_gpu_multi *m, int shard,
 		struct xsknf_gpu_shard_info *info);
 /* Copy shard `shard`'s UMEM span (span_hi - span_lo bytes), its rebased

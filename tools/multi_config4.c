@@ -5,7 +5,12 @@
  * links the CPU oracle (oracle/build/libcsum_oracle.so, pinned to the
  * reference's own function by tests/test_ref_pin.py) as the checker.
  *
- *   multi_config4 [frames (default 8388608)] [devices (default: all)]
+ *   multi_config4 [frames (default 8388608)] [devices (default: all)] [--device-descs]
+ *
+ * --device-descs (anywhere on the line): the descriptors are copied to device 0
+ * once and both scatters go through xsknf_gpu_multi_scatter_dev, which plans on
+ * the device; the JSON line gains plan_ms (the two calls' planning share) and
+ * device_descs, and span_scatter_ms / packed_scatter_ms then include the planning.
  *
  * The batch: IMIX 64 / 570 / 1500 B frames (7:4:1, shuffled), one per 2 KiB
  * chunk at +256 (aligned mode), Eth / IPv4 / UDP headers, random payload, built
@@ -109,6 +114,14 @@ static void host_counters(const uint8_t *umem, uint64_t umem_size, const struct 
 
 int main(int argc, char **argv)
 {
+	int dev_descs = 0, nargs = 1;
+	for (int a = 1; a < argc; a++) {   /* the option out of the way of the positional arguments */
+		if (!strcmp(argv[a], "--device-descs"))
+			dev_descs = 1;
+		else
+			argv[nargs++] = argv[a];
+	}
+	argc = nargs;
 	const uint64_t n = argc > 1 ? strtoull(argv[1], NULL, 0) : 8388608ull;
 	int ndev = 0;
 	XS_OK(xsknf_gpu_device_count(&ndev));
@@ -156,15 +169,24 @@ int main(int argc, char **argv)
 	HIP_OK(hipMalloc((void **)&umem, umem_size));
 	HIP_OK(hipMalloc((void **)&verdicts, sizeof(int32_t) * (n ? n : 1)));
 	HIP_OK(hipMemcpy(umem, host, umem_size, hipMemcpyHostToDevice));
+	struct xsknf_gpu_desc *ddescs = NULL;
+	if (dev_descs) {
+		HIP_OK(hipMalloc((void **)&ddescs, sizeof(*descs) * (n ? n : 1)));
+		HIP_OK(hipMemcpy(ddescs, descs, sizeof(*descs) * n, hipMemcpyHostToDevice));
+	}
 
 	struct xsknf_gpu_multi *m = NULL;
 	XS_OK(xsknf_gpu_multi_create(&m, NULL, ndev));
 	const struct xsknf_csum_opts o = {1, XSKNF_CSUM_ACTION_REDIRECT, 1, 0};
 
 	/* 1. the span path, in place on the shards, the counters all-reduced */
-	double t_span = 0;
+	double t_span = 0, t_plan_span = 0, t_plan_pack = 0;
 	float *ms = calloc(ndev, sizeof(float));
-	XS_OK(xsknf_gpu_multi_scatter(m, 0, umem, umem_size, descs, n, &t_span));
+	if (dev_descs)
+		XS_OK(xsknf_gpu_multi_scatter_dev(m, 0, umem, umem_size, ddescs, n, XSKNF_GPU_PLAN_SPAN, &t_span,
+						  &t_plan_span));
+	else
+		XS_OK(xsknf_gpu_multi_scatter(m, 0, umem, umem_size, descs, n, &t_span));
 	XS_OK(xsknf_gpu_multi_process(m, 0, &o, 1500, mean, ms));
 	uint64_t got[XSKNF_GPU_MULTI_COUNTERS];
 	XS_OK(xsknf_gpu_multi_counters(m, got));
@@ -179,7 +201,11 @@ int main(int argc, char **argv)
 	 * step_us_max above is this process's first pass (no warm-up). */
 	double t_pack = 0, t_ret = 0;
 	const double t0 = now();
-	XS_OK(xsknf_gpu_multi_scatter_packed(m, 0, umem, umem_size, descs, n, &t_pack));
+	if (dev_descs)
+		XS_OK(xsknf_gpu_multi_scatter_dev(m, 0, umem, umem_size, ddescs, n, XSKNF_GPU_PLAN_PACKED, &t_pack,
+						  &t_plan_pack));
+	else
+		XS_OK(xsknf_gpu_multi_scatter_packed(m, 0, umem, umem_size, descs, n, &t_pack));
 	XS_OK(xsknf_gpu_multi_return(m, 0, &o, 1500, mean, umem, verdicts, ms, &t_ret));
 	const double t_trip = now() - t0;
 	uint64_t moved = 0;
@@ -197,10 +223,16 @@ int main(int argc, char **argv)
 
 	printf("{\"frames\": %llu, \"devices\": %d, \"frame_bytes\": %llu, \"span_scatter_ms\": %.3f, "
 	       "\"step_us_max\": %.2f, \"counters_match\": %s, \"packed_scatter_ms\": %.3f, \"packed_bytes\": %llu, "
-	       "\"return_ms\": %.3f, \"packed_calls_wall_ms\": %.3f, \"root_umem_match\": %s, \"verdicts_match\": %s}\n",
+	       "\"return_ms\": %.3f, \"packed_calls_wall_ms\": %.3f, \"root_umem_match\": %s, \"verdicts_match\": %s",
 	       (unsigned long long)n, ndev, (unsigned long long)frame_bytes, t_span * 1e3, step_max * 1e3,
 	       counters_match ? "true" : "false", t_pack * 1e3, (unsigned long long)moved, t_ret * 1e3,
 	       t_trip * 1e3, umem_match ? "true" : "false", verdicts_match ? "true" : "false");
+	if (dev_descs)
+		printf(", \"device_descs\": true, \"plan_ms\": %.3f, \"span_plan_ms\": %.3f, \"packed_plan_ms\": %.3f",
+		       (t_plan_span + t_plan_pack) * 1e3, t_plan_span * 1e3, t_plan_pack * 1e3);
+	printf("}\n");
+	if (ddescs)
+		HIP_OK(hipFree(ddescs));
 	HIP_OK(hipFree(umem));
 	HIP_OK(hipFree(verdicts));
 	return counters_match && umem_match && verdicts_match ? 0 : 1;

@@ -40,9 +40,12 @@ EXPORTED_SYMBOLS = (
     "xsknf_gpu_shard_plan",
     "xsknf_gpu_shard_rebase",
     "xsknf_gpu_shard_pack_plan",
+    "xsknf_gpu_shard_plan_dev_workspace",
+    "xsknf_gpu_shard_plan_dev",
     "xsknf_gpu_multi_create",
     "xsknf_gpu_multi_scatter",
     "xsknf_gpu_multi_scatter_packed",
+    "xsknf_gpu_multi_scatter_dev",
     "xsknf_gpu_multi_return",
     "xsknf_gpu_multi_process",
     "xsknf_gpu_multi_counters",
@@ -96,6 +99,8 @@ class CtxStats(ctypes.Structure):
 
 
 SHARD_PACKED = 1   # XSKNF_GPU_SHARD_PACKED
+PLAN_SPAN = 0      # XSKNF_GPU_PLAN_SPAN
+PLAN_PACKED = 1    # XSKNF_GPU_PLAN_PACKED
 
 
 class ShardInfo(ctypes.Structure):
@@ -223,6 +228,14 @@ def load() -> ctypes.CDLL:
     lib.xsknf_gpu_multi_process.restype = ctypes.c_int
     lib.xsknf_gpu_multi_scatter_packed.restype = ctypes.c_int
     lib.xsknf_gpu_multi_scatter_packed.argtypes = [vp, ctypes.c_int, vp, u64, vp, u64, ctypes.POINTER(ctypes.c_double)]
+    lib.xsknf_gpu_shard_plan_dev_workspace.restype = ctypes.c_int
+    lib.xsknf_gpu_shard_plan_dev_workspace.argtypes = [u64, ctypes.c_uint32, ctypes.POINTER(u64)]
+    lib.xsknf_gpu_shard_plan_dev.restype = ctypes.c_int
+    lib.xsknf_gpu_shard_plan_dev.argtypes = [vp, u64, u64, u64, ctypes.c_uint32, ctypes.c_int, vp, vp, vp, vp, vp,
+                                             u64, vp]
+    lib.xsknf_gpu_multi_scatter_dev.restype = ctypes.c_int
+    lib.xsknf_gpu_multi_scatter_dev.argtypes = [vp, ctypes.c_int, vp, u64, vp, u64, ctypes.c_int,
+                                                ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
     lib.xsknf_gpu_multi_return.restype = ctypes.c_int
     lib.xsknf_gpu_multi_return.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(CsumOpts), ctypes.c_uint32,
                                            ctypes.c_uint32, vp, vp, vp, ctypes.POINTER(ctypes.c_double)]

@@ -35,6 +35,9 @@
 //     every final verdict: the root ends with the bytes and verdicts of one
 //     device's pass over the whole batch, having moved frames out and 4 bytes
 //     per frame back.
+//   * xsknf_gpu_multi_scatter_dev -- either scatter for descriptors that lie on
+//     the root device: planned there (plan_device.hip) instead of on the host,
+//     then the same placement and moves (place_shards / send_shards below).
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 #include <errno.h>
@@ -48,6 +51,7 @@
 
 #include "../../include/xsknf_gpu.h"
 #include "checksummer_internal.h"
+#include "plan_device.h"
 
 namespace {
 
@@ -241,6 +245,9 @@ struct xsknf_gpu_multi {
   uint64_t root_orig_cap = 0;
   uint8_t *root_pack = nullptr;
   uint64_t root_pack_cap = 0;
+  // the device planner's workspace (xsknf_gpu_multi_scatter_dev), on the root device too
+  uint8_t *root_plan = nullptr;
+  uint64_t root_plan_cap = 0;
 };
 
 namespace {
@@ -257,21 +264,19 @@ hipError_t root_buffer(T *&p, uint64_t &cap, uint64_t bytes) {
   return e;
 }
 
-// The root-side staging of a scatter: the device the root buffers live on
-// becomes devices[root] (buffers of an earlier root are freed), the caller's
-// descriptors go to root_orig (for the results' return) and `sent` (the
-// descriptors each shard receives, in global order) to root_descs.
-hipError_t stage_root(xsknf_gpu_multi *m, int root, const xsknf_gpu_desc *descs, const xsknf_gpu_desc *sent,
-                      uint64_t n) {
+// The root-side buffers of a scatter: the device the root buffers live on
+// becomes devices[root] (buffers of an earlier root are freed), root_orig and
+// root_descs hold n descriptors each.
+hipError_t root_prepare(xsknf_gpu_multi *m, int root, uint64_t n) {
   hipError_t e = hipSuccess;
   if (m->root_descs_dev >= 0 && m->root_descs_dev != m->devices[root]) {
     e = hipSetDevice(m->root_descs_dev);
     for (void *p : {static_cast<void *>(m->root_descs), static_cast<void *>(m->root_orig),
-                    static_cast<void *>(m->root_pack)})
+                    static_cast<void *>(m->root_pack), static_cast<void *>(m->root_plan)})
       if (e == hipSuccess && p) e = hipFree(p);
     m->root_descs = m->root_orig = nullptr;
-    m->root_pack = nullptr;
-    m->root_descs_cap = m->root_orig_cap = m->root_pack_cap = 0;
+    m->root_pack = m->root_plan = nullptr;
+    m->root_descs_cap = m->root_orig_cap = m->root_pack_cap = m->root_plan_cap = 0;
   }
   if (e == hipSuccess) e = hipSetDevice(m->devices[root]);
   m->root_descs_dev = m->devices[root];
@@ -281,6 +286,16 @@ hipError_t stage_root(xsknf_gpu_multi *m, int root, const xsknf_gpu_desc *descs,
   if (e == hipSuccess) e = root_buffer(m->root_orig, cap_o, bytes);
   m->root_descs_cap = cap_d / sizeof(xsknf_gpu_desc);
   m->root_orig_cap = cap_o / sizeof(xsknf_gpu_desc);
+  return e;
+}
+
+// The root-side staging of a scatter from host descriptors: the caller's
+// descriptors go to root_orig (for the results' return) and `sent` (the
+// descriptors each shard receives, in global order) to root_descs.
+hipError_t stage_root(xsknf_gpu_multi *m, int root, const xsknf_gpu_desc *descs, const xsknf_gpu_desc *sent,
+                      uint64_t n) {
+  hipError_t e = root_prepare(m, root, n);
+  const uint64_t bytes = sizeof(xsknf_gpu_desc) * n;
   if (e == hipSuccess && n) e = hipMemcpy(m->root_descs, sent, bytes, hipMemcpyHostToDevice);
   if (e == hipSuccess && n) e = hipMemcpy(m->root_orig, descs, bytes, hipMemcpyHostToDevice);
   return e;
@@ -350,6 +365,98 @@ int grouped_moves(xsknf_gpu_multi *m, const std::vector<Move> &moves, const char
   return 0;
 }
 
+// A scatter's plan as the host holds it, from shard_plan.cpp or the device
+// planner: the cuts, each shard's span (2 per shard) or packed bytes (1 per
+// shard), each shard's frame bytes.
+struct Plan {
+  bool packed = false;
+  std::vector<uint64_t> bounds, ext, bytes;
+};
+
+// The planned shards' fields and device buffers (packed: the root's staging
+// buffer too; pk_lo[k] = shard k's place in it).  After the root's staging.
+int place_shards(xsknf_gpu_multi *m, int root, const uint8_t *umem, const Plan &p, std::vector<uint64_t> &pk_lo) {
+  const int N = m->ndev;
+  if (p.packed) {
+    // the root's own shard is packed straight into its shard buffer; the staging
+    // buffer holds the others' (at N = 1 nothing is staged, nothing copied)
+    uint64_t total = 0;
+    pk_lo.assign(N, 0);
+    for (int k = 0; k < N; ++k) {
+      pk_lo[k] = k == root ? 0 : total;
+      total += k == root ? 0 : p.ext[k];
+    }
+    hipError_t e = root_buffer(m->root_pack, m->root_pack_cap, total);
+    if (e != hipSuccess) return hip_fail(e, "multi packed scatter: root buffers");
+  }
+  for (int k = 0; k < N; ++k) {
+    Shard &s = m->sh[k];
+    s.lo = p.bounds[k];
+    s.hi = p.bounds[k + 1];
+    s.b0 = p.packed ? 0 : p.ext[2 * k];
+    s.b1 = p.packed ? p.ext[k] : p.ext[2 * k + 1];
+    s.bytes = p.bytes[k];
+    hipError_t e = shard_buffers(s, s.b1 - s.b0, s.hi - s.lo,
+                                 p.packed ? 0 : reinterpret_cast<uintptr_t>(umem) + s.b0);
+    if (e != hipSuccess)
+      return hip_fail(e, p.packed ? "multi packed scatter: shard buffers" : "multi scatter: shard buffers");
+  }
+  return 0;
+}
+
+// The placed shards out of the root, root_descs and root_orig holding the
+// batch: (packed) the gather of every shard's frames on the root, then every
+// shard at once, one group.
+int send_shards(xsknf_gpu_multi *m, int root, const uint8_t *umem, uint64_t umem_size, uint64_t n, const Plan &p,
+                const std::vector<uint64_t> &pk_lo) {
+  const int N = m->ndev;
+  std::vector<Move> moves;
+  if (p.packed) {
+    // gather every shard's frames on the root, on the root's stream (its sends
+    // follow on the same stream): the root's own into its shard buffer
+    Shard &rs = m->sh[root];
+    hipError_t e = hipSetDevice(rs.device);
+    for (int k = 0; k < N && e == hipSuccess; ++k) {
+      const uint64_t frames = p.bounds[k + 1] - p.bounds[k];
+      if (!frames) continue;
+      const uint64_t want = (frames + 255) / 256;
+      const unsigned grid = static_cast<unsigned>(want < 4096 ? want : 4096);
+      hipLaunchKernelGGL(pack_frames, dim3(grid), dim3(256), 0, rs.stream, umem, umem_size,
+                         m->root_orig + p.bounds[k], m->root_descs + p.bounds[k], frames,
+                         k == root ? rs.umem : m->root_pack + pk_lo[k]);
+      e = hipGetLastError();
+    }
+    if (e != hipSuccess) return hip_fail(e, "multi packed scatter: pack_frames");
+  }
+  // the root sends each its span (packed: its packed frames) and descriptors,
+  // every device receives its own; the root's own span and descriptors go as a
+  // send to itself, so the path is the same at N = 1
+  for (int k = 0; k < N; ++k) {
+    Shard &s = m->sh[k];
+    if (!p.packed)
+      moves.push_back({umem + s.b0, s.umem, s.b1 - s.b0, root, k});
+    else if (k != root)
+      moves.push_back({m->root_pack + pk_lo[k], s.umem, p.ext[k], root, k});
+    moves.push_back({reinterpret_cast<const uint8_t *>(m->root_descs + s.lo), reinterpret_cast<uint8_t *>(s.descs),
+                     sizeof(xsknf_gpu_desc) * (s.hi - s.lo), root, k});
+  }
+  const int rc = grouped_moves(m, moves, p.packed ? "multi packed scatter: ncclSend / ncclRecv"
+                                                  : "multi scatter: ncclSend / ncclRecv");
+  if (rc) return rc;
+  m->root = root;
+  m->n = n;
+  m->processed = false;
+  m->packed = p.packed;
+  return 0;
+}
+
+// Each shard's sum of frame lengths, from host descriptors.
+void host_shard_bytes(const xsknf_gpu_desc *descs, Plan &p) {
+  p.bytes.assign(p.bounds.size() - 1, 0);
+  for (size_t k = 0; k + 1 < p.bounds.size(); ++k)
+    for (uint64_t f = p.bounds[k]; f < p.bounds[k + 1]; ++f) p.bytes[k] += descs[f].len;
+}
+
 }  // namespace
 
 extern "C" {
@@ -399,45 +506,27 @@ int xsknf_gpu_multi_scatter(struct xsknf_gpu_multi *m, int root, const uint8_t *
                             const struct xsknf_gpu_desc *descs, uint64_t n, double *seconds) {
   if (!m || root < 0 || root >= m->ndev || (n && (!umem || !descs))) return -EINVAL;
   const int N = m->ndev;
-  std::vector<uint64_t> bounds(N + 1), spans(2 * N);
-  int rc = xsknf_gpu_shard_plan(descs, n, umem_size, static_cast<uint32_t>(N), bounds.data(), spans.data());
+  Plan p;
+  p.bounds.resize(N + 1);
+  p.ext.resize(2 * N);
+  int rc = xsknf_gpu_shard_plan(descs, n, umem_size, static_cast<uint32_t>(N), p.bounds.data(), p.ext.data());
   if (rc) return rc;
   // the rebased descriptors of every shard (each relative to its own span),
   // staged on the root device in global order
   std::vector<xsknf_gpu_desc> rebased(n);
   for (int k = 0; k < N; ++k)
-    xsknf_gpu_shard_rebase(descs + bounds[k], bounds[k + 1] - bounds[k], spans[2 * k], umem_size,
-                           rebased.data() + bounds[k]);
+    xsknf_gpu_shard_rebase(descs + p.bounds[k], p.bounds[k + 1] - p.bounds[k], p.ext[2 * k], umem_size,
+                           rebased.data() + p.bounds[k]);
   hipError_t e = stage_root(m, root, descs, rebased.data(), n);
   if (e != hipSuccess) return hip_fail(e, "multi scatter: root descriptors");
-  for (int k = 0; k < N; ++k) {
-    Shard &s = m->sh[k];
-    s.lo = bounds[k];
-    s.hi = bounds[k + 1];
-    s.b0 = spans[2 * k];
-    s.b1 = spans[2 * k + 1];
-    s.bytes = 0;
-    for (uint64_t f = s.lo; f < s.hi; ++f) s.bytes += descs[f].len;
-    e = shard_buffers(s, s.b1 - s.b0, s.hi - s.lo, reinterpret_cast<uintptr_t>(umem) + s.b0);
-    if (e != hipSuccess) return hip_fail(e, "multi scatter: shard buffers");
-  }
-  // every shard at once: the root sends each its span and descriptors, every
-  // device receives its own (the root's to itself), one group
+  host_shard_bytes(descs, p);
+  std::vector<uint64_t> pk_lo;
+  rc = place_shards(m, root, umem, p, pk_lo);
+  if (rc) return rc;
   const double t0 = now_s();
-  std::vector<Move> moves;
-  for (int k = 0; k < N; ++k) {
-    Shard &s = m->sh[k];
-    moves.push_back({umem + s.b0, s.umem, s.b1 - s.b0, root, k});
-    moves.push_back({reinterpret_cast<const uint8_t *>(m->root_descs + s.lo), reinterpret_cast<uint8_t *>(s.descs),
-                     sizeof(xsknf_gpu_desc) * (s.hi - s.lo), root, k});
-  }
-  rc = grouped_moves(m, moves, "multi scatter: ncclSend / ncclRecv");
+  rc = send_shards(m, root, umem, umem_size, n, p, pk_lo);
   if (rc) return rc;
   if (seconds) *seconds = now_s() - t0;
-  m->root = root;
-  m->n = n;
-  m->processed = false;
-  m->packed = false;
   return 0;
 }
 
@@ -445,65 +534,64 @@ int xsknf_gpu_multi_scatter_packed(struct xsknf_gpu_multi *m, int root, const ui
                                    const struct xsknf_gpu_desc *descs, uint64_t n, double *seconds) {
   if (!m || root < 0 || root >= m->ndev || (n && (!umem || !descs))) return -EINVAL;
   const int N = m->ndev;
-  std::vector<uint64_t> bounds(N + 1);
-  int rc = xsknf_gpu_shard_plan(descs, n, umem_size, static_cast<uint32_t>(N), bounds.data(), nullptr);
+  Plan p;
+  p.packed = true;
+  p.bounds.resize(N + 1);
+  p.ext.resize(N);
+  int rc = xsknf_gpu_shard_plan(descs, n, umem_size, static_cast<uint32_t>(N), p.bounds.data(), nullptr);
   if (rc) return rc;
   std::vector<xsknf_gpu_desc> packed(n);
-  std::vector<uint64_t> pk_lo(N), pk_size(N);
   rc = xsknf_gpu_shard_pack_plan(descs, n, reinterpret_cast<uintptr_t>(umem), umem_size, static_cast<uint32_t>(N),
-                                 bounds.data(), packed.data(), pk_size.data());
+                                 p.bounds.data(), packed.data(), p.ext.data());
   if (rc) return rc;
-  // the root's own shard is packed straight into its shard buffer; the staging
-  // buffer holds the others' (at N = 1 nothing is staged, nothing copied)
-  uint64_t total = 0;
-  for (int k = 0; k < N; ++k) {
-    pk_lo[k] = k == root ? 0 : total;
-    total += k == root ? 0 : pk_size[k];
-  }
   hipError_t e = stage_root(m, root, descs, packed.data(), n);
-  if (e == hipSuccess) e = root_buffer(m->root_pack, m->root_pack_cap, total);
   if (e != hipSuccess) return hip_fail(e, "multi packed scatter: root buffers");
-  for (int k = 0; k < N; ++k) {
-    Shard &s = m->sh[k];
-    s.lo = bounds[k];
-    s.hi = bounds[k + 1];
-    s.b0 = 0;
-    s.b1 = pk_size[k];
-    s.bytes = 0;
-    for (uint64_t f = s.lo; f < s.hi; ++f) s.bytes += descs[f].len;
-    e = shard_buffers(s, pk_size[k], s.hi - s.lo, 0);
-    if (e != hipSuccess) return hip_fail(e, "multi packed scatter: shard buffers");
-  }
+  host_shard_bytes(descs, p);
+  std::vector<uint64_t> pk_lo;
+  rc = place_shards(m, root, umem, p, pk_lo);
+  if (rc) return rc;
   const double t0 = now_s();
-  // gather every shard's frames on the root, on the root's stream (its sends
-  // follow on the same stream): the root's own into its shard buffer
-  Shard &rs = m->sh[root];
-  e = hipSetDevice(rs.device);
-  for (int k = 0; k < N && e == hipSuccess; ++k) {
-    const uint64_t frames = bounds[k + 1] - bounds[k];
-    if (!frames) continue;
-    const uint64_t want = (frames + 255) / 256;
-    const unsigned grid = static_cast<unsigned>(want < 4096 ? want : 4096);
-    hipLaunchKernelGGL(pack_frames, dim3(grid), dim3(256), 0, rs.stream, umem, umem_size, m->root_orig + bounds[k],
-                       m->root_descs + bounds[k], frames, k == root ? rs.umem : m->root_pack + pk_lo[k]);
-    e = hipGetLastError();
-  }
-  if (e != hipSuccess) return hip_fail(e, "multi packed scatter: pack_frames");
-  std::vector<Move> moves;
-  for (int k = 0; k < N; ++k) {
-    Shard &s = m->sh[k];
-    if (k != root) moves.push_back({m->root_pack + pk_lo[k], s.umem, pk_size[k], root, k});
-    // (the root's descriptors too, as a send to itself: the same path at N = 1)
-    moves.push_back({reinterpret_cast<const uint8_t *>(m->root_descs + s.lo), reinterpret_cast<uint8_t *>(s.descs),
-                     sizeof(xsknf_gpu_desc) * (s.hi - s.lo), root, k});
-  }
-  rc = grouped_moves(m, moves, "multi packed scatter: ncclSend / ncclRecv");
+  rc = send_shards(m, root, umem, umem_size, n, p, pk_lo);
   if (rc) return rc;
   if (seconds) *seconds = now_s() - t0;
-  m->root = root;
-  m->n = n;
-  m->processed = false;
-  m->packed = true;
+  return 0;
+}
+
+int xsknf_gpu_multi_scatter_dev(struct xsknf_gpu_multi *m, int root, const uint8_t *umem, uint64_t umem_size,
+                                const struct xsknf_gpu_desc *descs_dev, uint64_t n, int mode, double *seconds,
+                                double *plan_seconds) {
+  if (!m || root < 0 || root >= m->ndev || (n && (!umem || !descs_dev))) return -EINVAL;
+  if (mode != XSKNF_GPU_PLAN_SPAN && mode != XSKNF_GPU_PLAN_PACKED) return -EINVAL;
+  if (reinterpret_cast<uintptr_t>(descs_dev) & 15) return -EINVAL;   // the planner's 16-byte loads
+  const int N = m->ndev;
+  const double t0 = now_s();
+  Plan p;
+  p.packed = mode == XSKNF_GPU_PLAN_PACKED;
+  p.bounds.resize(N + 1);
+  p.ext.resize(p.packed ? N : 2 * N);
+  p.bytes.resize(N);
+  const char *what = "multi device-planned scatter: root buffers";
+  hipError_t e = root_prepare(m, root, n);
+  if (e == hipSuccess) e = root_buffer(m->root_plan, m->root_plan_cap, xsknf_gpu::plan_dev_workspace_bytes(n));
+  if (e != hipSuccess) return hip_fail(e, what);
+  // the plan, straight into root_descs, on the root's stream
+  Shard &rs = m->sh[root];
+  const double tp = now_s();
+  int rc = xsknf_gpu::plan_dev_run(descs_dev, n, reinterpret_cast<uintptr_t>(umem), umem_size,
+                                   static_cast<uint32_t>(N), mode, m->root_descs, p.bounds.data(), p.ext.data(),
+                                   p.bytes.data(), m->root_plan, rs.stream);
+  if (rc) return rc;
+  if (plan_seconds) *plan_seconds = now_s() - tp;
+  // the caller's descriptors for the results' return (ahead of pack_frames on
+  // the same stream; send_shards waits for the stream before it returns)
+  if (n) e = hipMemcpyAsync(m->root_orig, descs_dev, sizeof(xsknf_gpu_desc) * n, hipMemcpyDeviceToDevice, rs.stream);
+  if (e != hipSuccess) return hip_fail(e, "multi device-planned scatter: descriptor copy");
+  std::vector<uint64_t> pk_lo;
+  rc = place_shards(m, root, umem, p, pk_lo);
+  if (rc) return rc;
+  rc = send_shards(m, root, umem, umem_size, n, p, pk_lo);
+  if (rc) return rc;
+  if (seconds) *seconds = now_s() - t0;
   return 0;
 }
 
@@ -684,6 +772,7 @@ int xsknf_gpu_multi_destroy(struct xsknf_gpu_multi *m) {
     if (m->root_descs) (void)hipFree(m->root_descs);
     if (m->root_orig) (void)hipFree(m->root_orig);
     if (m->root_pack) (void)hipFree(m->root_pack);
+    if (m->root_plan) (void)hipFree(m->root_plan);
   }
   for (ncclComm_t c : m->comms)
     if (c) (void)ncclCommDestroy(c);

@@ -67,6 +67,42 @@ def pack_plan(descs, bounds, umem_addr: int, umem_size: int):
     return out, [int(x) for x in sizes]
 
 
+def plan_dev_workspace(n: int, nshards: int = 1) -> int:
+    """Bytes of device workspace shard_plan_dev needs for n descriptors (no GPU)."""
+    out = ctypes.c_uint64()
+    _lib.check(_lib.load().xsknf_gpu_shard_plan_dev_workspace(n, nshards, ctypes.byref(out)),
+               "xsknf_gpu_shard_plan_dev_workspace")
+    return int(out.value)
+
+
+def shard_plan_dev(descs_ptr: int, n: int, nshards: int, umem_addr: int, umem_size: int, mode: int = _lib.PLAN_SPAN,
+                   device=None):
+    """xsknf_gpu_shard_plan_dev: the plan of n descriptors at device pointer
+    descs_ptr, computed on that device (`device`: a torch device, default the
+    current one).  Returns ([(lo, hi)] frame ranges, [(b0, b1)] spans for
+    PLAN_SPAN or [packed bytes] for PLAN_PACKED, [frame bytes per shard], the
+    output descriptors as an (n, 2) int64 device tensor of 16-byte records)."""
+    import torch
+    lib = _lib.load()
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    packed = mode == _lib.PLAN_PACKED
+    bounds = np.zeros(nshards + 1, dtype=np.uint64)
+    aux = np.zeros(nshards if packed else 2 * nshards, dtype=np.uint64)
+    fbytes = np.zeros(nshards, dtype=np.uint64)
+    with torch.cuda.device(dev):
+        out = torch.empty((n, 2), dtype=torch.int64, device=dev)
+        ws = torch.empty(plan_dev_workspace(n, nshards) // 8, dtype=torch.int64, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(lib.xsknf_gpu_shard_plan_dev(ctypes.c_void_p(descs_ptr) if n else None, n, umem_addr, umem_size,
+                                                nshards, mode, ctypes.c_void_p(out.data_ptr()) if n else None,
+                                                bounds.ctypes.data, aux.ctypes.data, fbytes.ctypes.data,
+                                                ctypes.c_void_p(ws.data_ptr()), ws.numel() * 8,
+                                                ctypes.c_void_p(stream)), "xsknf_gpu_shard_plan_dev")
+    ranges = [(int(bounds[k]), int(bounds[k + 1])) for k in range(nshards)]
+    ext = [int(x) for x in aux] if packed else [(int(aux[2 * k]), int(aux[2 * k + 1])) for k in range(nshards)]
+    return ranges, ext, [int(x) for x in fbytes], out
+
+
 class MultiDevice:
     """xsknf_gpu_multi over `devices` (HIP device ids, each once)."""
 
@@ -110,6 +146,18 @@ class MultiDevice:
                                                             int(d.shape[0]), ctypes.byref(secs)),
                    "xsknf_gpu_multi_scatter_packed")
         return secs.value
+
+    def scatter_dev(self, root: int, umem_ptr: int, umem_size: int, descs_ptr: int, n: int, packed: bool = False):
+        """scatter() / scatter_packed() for n descriptors at device pointer
+        descs_ptr on devices[root], planned on that device
+        (xsknf_gpu_multi_scatter_dev); (seconds with the planning, the planning's seconds)."""
+        secs, plan = ctypes.c_double(), ctypes.c_double()
+        _lib.check(self._lib.xsknf_gpu_multi_scatter_dev(self._h, root, ctypes.c_void_p(umem_ptr), umem_size,
+                                                         ctypes.c_void_p(descs_ptr) if n else None, int(n),
+                                                         _lib.PLAN_PACKED if packed else _lib.PLAN_SPAN,
+                                                         ctypes.byref(secs), ctypes.byref(plan)),
+                   "xsknf_gpu_multi_scatter_dev")
+        return secs.value, plan.value
 
     def return_results(self, umem_ptr: int, verdicts_ptr: int, opts: ChecksummerOptions | None = None,
                        num_interfaces: int = 1, ingress_ifindex: int = 0, frame_len_max: int = 0,
