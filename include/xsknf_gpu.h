@@ -480,6 +480,75 @@ XSKNF_GPU_API int xsknf_gpu_multi_fetch(const struct xsknf_gpu_multi *m, int sha
 		struct xsknf_gpu_desc *descs_out, int32_t *verdicts_out);
 XSKNF_GPU_API int xsknf_gpu_multi_destroy(struct xsknf_gpu_multi *m);
 
+/* ---- routing a checksummed batch: per-interface tx lists and the fill list ----
+ * The second half of the reference's batch loop (process_batch, src/xsknf.c:
+ * 503-522, and process_batch_1if, :654-672) for a batch whose verdicts are
+ * known: every frame is filed by its verdict, a dropped frame into to_drop[]
+ * and any other into to_tx[verdict][], in receive order, and those lists are
+ * what goes into the fill ring (u64 addr, :538-540, :685-687) and into the
+ * destination's tx ring ({addr, len}, :573-578, :706-709).  The checksum calls
+ * above and xsknf_gpu_multi_return leave one int32 verdict per frame next to the
+ * descriptors, in device memory; these calls turn that state into ring-ready
+ * lists, on the device or (the model the device is held to) on one CPU thread,
+ * with the same result bit for bit.
+ *
+ * The bin of frame f (D = drop):
+ *   num_interfaces == 1   process_batch_1if's rule (xsknf_rt.c dispose_1if):
+ *                         verdicts[f] == -1 gives D, any other value interface 0;
+ *   num_interfaces > 1    xsknf_rt.c dispose_multi's: v < 0 or (uint32_t)v >=
+ *                         num_interfaces gives D, else interface v (the reference
+ *                         would index to_tx[] with such a v unchecked).
+ * counts[i], i < num_interfaces, is the number of frames in bin i and
+ * counts[num_interfaces] the number of dropped frames; base_i = counts[0] + ... +
+ * counts[i - 1], ntx = the sum over all interfaces.  The partition is stable:
+ * with r the number of frames g < f in f's bin,
+ *   a tx frame of bin i  tx_descs[base_i + r] = {descs[f].addr, descs[f].len, 0}
+ *                        (the address as received, untranslated: `orig`, :507;
+ *                        options 0), and order[base_i + r] = f;
+ *   a dropped frame      fill_addrs[r] = descs[f].addr, and order[ntx + r] = f.
+ * Interface i's tx list is tx_descs[base_i .. base_i + counts[i]).  Entries of
+ * tx_descs at or past ntx and of fill_addrs at or past the drop count are not
+ * written; descs and verdicts are only read.  The outputs must not overlap the
+ * inputs or each other.  `order` (may be NULL) is what a gather of the frames'
+ * bytes into another UMEM (the copy of :563-571, not done here) would consume.
+ *
+ * A record left by a records-only pass (fused_stores 3: a word tagged
+ * XSKNF_GPU_RECORD_TAG, 0x4...) is NOT a verdict: apply the records first (as
+ * xsknf_gpu_multi_return and the STAGED host path do); routed as it stands, such
+ * a word is just a value that names no interface. */
+#define XSKNF_GPU_ROUTE_MAX_INTERFACES 32   /* XSKNF_MAX_INTERFACES, src/xsknf.h:11 */
+
+/* *bytes = the device workspace xsknf_gpu_route_batch needs for n frames
+ * (positive, non-decreasing in n).  Host arithmetic; no GPU call.  -EINVAL for
+ * num_interfaces 0 or > 32 or a NULL bytes. */
+XSKNF_GPU_API int xsknf_gpu_route_workspace(uint32_t n, uint32_t num_interfaces, uint64_t *bytes);
+/* Route n frames on the current device, on `stream` (a hipStream_t; NULL: the
+ * default stream).  descs (16-byte aligned) and verdicts are device memory, as
+ * are tx_descs (n records, 16-byte aligned), fill_addrs (n words), order (n
+ * words, may be NULL) and workspace (8-byte aligned, workspace_bytes >= what
+ * _workspace reports for n and num_interfaces).
+ * counts (HOST memory, num_interfaces + 1 words, may be NULL):
+ *   given   filled when the call returns: the call waits for `stream`;
+ *   NULL    the call only enqueues; the same num_interfaces + 1 words are the
+ *           first u64 words of `workspace` once the stream gets there (they are
+ *           there in either case).
+ * n == 0 succeeds without a launch: a given counts is all 0, nothing else is
+ * written (the workspace neither, and it may be NULL).
+ * -EINVAL, before any GPU call: num_interfaces 0 or > 32; descs or tx_descs not
+ * 16-byte aligned, fill_addrs or workspace not 8-byte aligned, verdicts or order
+ * not 4-byte aligned; and with n > 0 a NULL descs, verdicts, tx_descs,
+ * fill_addrs or workspace, or a workspace too small.  -EIO on a HIP error, with
+ * xsknf_gpu_last_error() set. */
+XSKNF_GPU_API int xsknf_gpu_route_batch(const struct xsknf_gpu_desc *descs, const int32_t *verdicts, uint32_t n,
+		uint32_t num_interfaces, struct xsknf_gpu_desc *tx_descs, uint64_t *fill_addrs, uint32_t *order,
+		uint64_t *counts, void *workspace, uint64_t workspace_bytes, void *stream);
+/* The same on host arrays, one thread, no GPU call.  -EINVAL for num_interfaces
+ * 0 or > 32 and, with n > 0, a NULL descs, verdicts, tx_descs or fill_addrs
+ * (order and counts may be NULL). */
+XSKNF_GPU_API int xsknf_gpu_route_host(const struct xsknf_gpu_desc *descs, const int32_t *verdicts, uint32_t n,
+		uint32_t num_interfaces, struct xsknf_gpu_desc *tx_descs, uint64_t *fill_addrs, uint32_t *order,
+		uint64_t *counts);
+
 /* Text of the last HIP error seen by this library, on any thread (a copy
  * private to the calling thread). */
 XSKNF_GPU_API const char *xsknf_gpu_last_error(void);

@@ -5,12 +5,19 @@
  * links the CPU oracle (oracle/build/libcsum_oracle.so, pinned to the
  * reference's own function by tests/test_ref_pin.py) as the checker.
  *
- *   multi_config4 [frames (default 8388608)] [devices (default: all)] [--device-descs]
+ *   multi_config4 [frames (default 8388608)] [devices (default: all)] [--device-descs] [--route]
  *
  * --device-descs (anywhere on the line): the descriptors are copied to device 0
  * once and both scatters go through xsknf_gpu_multi_scatter_dev, which plans on
  * the device; the JSON line gains plan_ms (the two calls' planning share) and
  * device_descs, and span_scatter_ms / packed_scatter_ms then include the planning.
+ *
+ * --route: after the packed round trip the root's verdicts are routed on
+ * device 0 (xsknf_gpu_route_batch: the tx list and the fill list, with `order`)
+ * and every count and list entry is compared with xsknf_gpu_route_host over
+ * the oracle's verdicts; the JSON line gains route_match and route_ms (one
+ * warmed call with its counts read back, on the host's clock), and the exit
+ * status covers route_match.
  *
  * The batch: IMIX 64 / 570 / 1500 B frames (7:4:1, shuffled), one per 2 KiB
  * chunk at +256 (aligned mode), Eth / IPv4 / UDP headers, random payload, built
@@ -112,12 +119,59 @@ static void host_counters(const uint8_t *umem, uint64_t umem_size, const struct 
 	}
 }
 
+/* --route: the verdicts at `verdicts` (device 0, beside the descriptors at
+ * ddescs) routed there, one interface as the pass above ran; every count and
+ * every entry of the lists against xsknf_gpu_route_host over the oracle's
+ * verdicts.  *seconds: the second of two calls, its counts read back. */
+static int route_check(const struct xsknf_gpu_desc *ddescs, const int32_t *verdicts,
+		       const struct xsknf_gpu_desc *descs, const int32_t *ov, uint32_t n, double *seconds)
+{
+	const uint32_t nif = 1;
+	const size_t m = n ? n : 1;
+	uint64_t ws_bytes = 0, got[2] = {~0ull, ~0ull}, want[2] = {0, 0};
+	struct xsknf_gpu_desc *dtx = NULL, *tx = malloc(sizeof(*tx) * m), *wtx = malloc(sizeof(*wtx) * m);
+	uint64_t *dfill = NULL, *fill = malloc(sizeof(uint64_t) * m), *wfill = malloc(sizeof(uint64_t) * m);
+	uint32_t *dorder = NULL, *order = malloc(sizeof(uint32_t) * m), *worder = malloc(sizeof(uint32_t) * m);
+	void *ws = NULL;
+	if (!tx || !wtx || !fill || !wfill || !order || !worder) {
+		fprintf(stderr, "out of host memory\n");
+		exit(2);
+	}
+	XS_OK(xsknf_gpu_route_workspace(n, nif, &ws_bytes));
+	HIP_OK(hipMalloc((void **)&dtx, sizeof(*dtx) * m));
+	HIP_OK(hipMalloc((void **)&dfill, sizeof(uint64_t) * m));
+	HIP_OK(hipMalloc((void **)&dorder, sizeof(uint32_t) * m));
+	HIP_OK(hipMalloc(&ws, ws_bytes));
+	XS_OK(xsknf_gpu_route_batch(ddescs, verdicts, n, nif, dtx, dfill, dorder, got, ws, ws_bytes, NULL));
+	const double t0 = now();
+	XS_OK(xsknf_gpu_route_batch(ddescs, verdicts, n, nif, dtx, dfill, dorder, got, ws, ws_bytes, NULL));
+	*seconds = now() - t0;
+	HIP_OK(hipMemcpy(tx, dtx, sizeof(*tx) * n, hipMemcpyDeviceToHost));
+	HIP_OK(hipMemcpy(fill, dfill, sizeof(uint64_t) * n, hipMemcpyDeviceToHost));
+	HIP_OK(hipMemcpy(order, dorder, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+	XS_OK(xsknf_gpu_route_host(descs, ov, n, nif, wtx, wfill, worder, want));
+	int ok = got[0] == want[0] && got[1] == want[1] && want[0] + want[1] == n;
+	for (uint64_t i = 0; ok && i < want[0]; i++)
+		ok = tx[i].addr == wtx[i].addr && tx[i].len == wtx[i].len && tx[i].options == wtx[i].options;
+	for (uint64_t i = 0; ok && i < want[1]; i++)
+		ok = fill[i] == wfill[i];
+	ok = ok && !memcmp(order, worder, sizeof(uint32_t) * n);
+	HIP_OK(hipFree(dtx));
+	HIP_OK(hipFree(dfill));
+	HIP_OK(hipFree(dorder));
+	HIP_OK(hipFree(ws));
+	free(tx); free(wtx); free(fill); free(wfill); free(order); free(worder);
+	return ok;
+}
+
 int main(int argc, char **argv)
 {
-	int dev_descs = 0, nargs = 1;
+	int dev_descs = 0, do_route = 0, nargs = 1;
 	for (int a = 1; a < argc; a++) {   /* the option out of the way of the positional arguments */
 		if (!strcmp(argv[a], "--device-descs"))
 			dev_descs = 1;
+		else if (!strcmp(argv[a], "--route"))
+			do_route = 1;
 		else
 			argv[nargs++] = argv[a];
 	}
@@ -170,7 +224,7 @@ int main(int argc, char **argv)
 	HIP_OK(hipMalloc((void **)&verdicts, sizeof(int32_t) * (n ? n : 1)));
 	HIP_OK(hipMemcpy(umem, host, umem_size, hipMemcpyHostToDevice));
 	struct xsknf_gpu_desc *ddescs = NULL;
-	if (dev_descs) {
+	if (dev_descs || do_route) {
 		HIP_OK(hipMalloc((void **)&ddescs, sizeof(*descs) * (n ? n : 1)));
 		HIP_OK(hipMemcpy(ddescs, descs, sizeof(*descs) * n, hipMemcpyHostToDevice));
 	}
@@ -216,6 +270,10 @@ int main(int argc, char **argv)
 	}
 	XS_OK(xsknf_gpu_multi_destroy(m));
 	HIP_OK(hipSetDevice(0));
+	int route_match = 1;
+	double t_route = 0;
+	if (do_route)
+		route_match = route_check(ddescs, verdicts, descs, ov, (uint32_t)n, &t_route);
 	HIP_OK(hipMemcpy(back, umem, umem_size, hipMemcpyDeviceToHost));
 	HIP_OK(hipMemcpy(gv, verdicts, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
 	const int umem_match = !memcmp(back, ref, umem_size);
@@ -230,10 +288,12 @@ int main(int argc, char **argv)
 	if (dev_descs)
 		printf(", \"device_descs\": true, \"plan_ms\": %.3f, \"span_plan_ms\": %.3f, \"packed_plan_ms\": %.3f",
 		       (t_plan_span + t_plan_pack) * 1e3, t_plan_span * 1e3, t_plan_pack * 1e3);
+	if (do_route)
+		printf(", \"route_match\": %s, \"route_ms\": %.3f", route_match ? "true" : "false", t_route * 1e3);
 	printf("}\n");
 	if (ddescs)
 		HIP_OK(hipFree(ddescs));
 	HIP_OK(hipFree(umem));
 	HIP_OK(hipFree(verdicts));
-	return counters_match && umem_match && verdicts_match ? 0 : 1;
+	return counters_match && umem_match && verdicts_match && route_match ? 0 : 1;
 }

@@ -52,7 +52,12 @@ EXPORTED_SYMBOLS = (
     "xsknf_gpu_multi_shard_info",
     "xsknf_gpu_multi_fetch",
     "xsknf_gpu_multi_destroy",
+    "xsknf_gpu_route_workspace",
+    "xsknf_gpu_route_batch",
+    "xsknf_gpu_route_host",
 )
+
+ROUTE_MAX_INTERFACES = 32   # XSKNF_GPU_ROUTE_MAX_INTERFACES
 
 MULTI_COUNTERS = 6   # XSKNF_GPU_MULTI_COUNTERS
 
@@ -249,6 +254,12 @@ def load() -> ctypes.CDLL:
     lib.xsknf_gpu_multi_fetch.argtypes = [vp, ctypes.c_int, vp, vp, vp]
     lib.xsknf_gpu_multi_destroy.restype = ctypes.c_int
     lib.xsknf_gpu_multi_destroy.argtypes = [vp]
+    lib.xsknf_gpu_route_workspace.restype = ctypes.c_int
+    lib.xsknf_gpu_route_workspace.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(u64)]
+    lib.xsknf_gpu_route_batch.restype = ctypes.c_int
+    lib.xsknf_gpu_route_batch.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, vp, vp, u64, vp]
+    lib.xsknf_gpu_route_host.restype = ctypes.c_int
+    lib.xsknf_gpu_route_host.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, vp]
     lib.xsknf_gpu_pool_guard_trips.restype = ctypes.c_int
     lib.xsknf_gpu_pool_guard_trips.argtypes = [ctypes.POINTER(ctypes.c_uint32), ctypes.c_int]
     _lib = lib

@@ -165,6 +165,15 @@ class Checksummer:
                                    frame_len_hint)
         return verdicts
 
+    def route(self, descs, verdicts, order: bool = False):
+        """The other half of the batch loop (src/xsknf.c:503-522, :654-672), on
+        the device: the batch's frames filed by the verdicts process_batch left,
+        one tx list per interface of this object and the fill list of the drops
+        (route.route_batch: tx_descs, fill_addrs, order or None, counts)."""
+        from . import route as _route
+
+        return _route.route_batch(descs, verdicts, self.num_interfaces, order=order)
+
 
 class HostPath:
     """The batch hook with the UMEM in host memory (include/xsknf_gpu.h

@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "../../include/xsknf_gpu.h"
+#include "block_scan.h"
 
 namespace xsknf_gpu {
 namespace plan {
@@ -76,27 +77,9 @@ __device__ inline uint64_t slot_len(uint64_t umem_addr, uint64_t off, uint32_t l
   return (((umem_addr + off) & 15) + len + 15) & ~15ull;
 }
 
-// Inclusive scan of one u64 per thread over the block; *total = the block's sum.
-// wtot: 4 words of LDS.  Every thread of the block calls it.
-__device__ inline uint64_t block_incl_scan(uint64_t x, uint64_t *wtot, uint64_t *total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint64_t y = __shfl_up(x, o);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) wtot[wv] = x;
-  __syncthreads();
-  uint64_t pre = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < kThreads / 64; ++w) {
-    const uint64_t t = wtot[w];
-    if (w < wv) pre += t;
-    tot += t;
-  }
-  __syncthreads();   // wtot is rewritten by the next scan
-  *total = tot;
-  return pre + x;
-}
+// The u64 block scan (block_scan.h), shared with the router's kernels.
+static_assert(scan::kThreads == kThreads, "block_incl_scan scans a block of kThreads");
+using scan::block_incl_scan;
 
 // The shard of frame f: the last k < nshards with sb[k] <= f (empty shards
 // share a bound with their successor; f < sb[nshards]).
