@@ -5,7 +5,8 @@ HIPFLAGS ?= -O3 -std=c++17 -fPIC -Wall -Wno-inline-asm -fvisibility=hidden --off
 LIBDIR := xsknf_amd/lib
 LIB := $(LIBDIR)/libxsknf_gpu.so
 SRCS := xsknf_amd/csrc/checksummer.hip xsknf_amd/csrc/host_path.hip xsknf_amd/csrc/multi.hip xsknf_amd/csrc/plan_device.hip \
-	xsknf_amd/csrc/route_device.hip xsknf_amd/csrc/shard_plan.cpp xsknf_amd/csrc/route_host.cpp
+	xsknf_amd/csrc/route_device.hip xsknf_amd/csrc/forward_device.hip xsknf_amd/csrc/shard_plan.cpp xsknf_amd/csrc/route_host.cpp \
+	xsknf_amd/csrc/forward_host.cpp
 # every header the device code may include: checksummer.hip is one translation
 # unit over csum_device.h and the kernel_*.h families
 GPUHDRS := include/xsknf_gpu.h include/xsknf.h $(wildcard xsknf_amd/csrc/*.h)

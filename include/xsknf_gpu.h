@@ -510,7 +510,8 @@ XSKNF_GPU_API int xsknf_gpu_multi_destroy(struct xsknf_gpu_multi *m);
  * tx_descs at or past ntx and of fill_addrs at or past the drop count are not
  * written; descs and verdicts are only read.  The outputs must not overlap the
  * inputs or each other.  `order` (may be NULL) is what a gather of the frames'
- * bytes into another UMEM (the copy of :563-571, not done here) would consume.
+ * bytes into a packed buffer would consume (the copy of :563-571 into another
+ * UMEM needs only the lists: xsknf_gpu_forward_frames below).
  *
  * A record left by a records-only pass (fused_stores 3: a word tagged
  * XSKNF_GPU_RECORD_TAG, 0x4...) is NOT a verdict: apply the records first (as
@@ -548,6 +549,73 @@ XSKNF_GPU_API int xsknf_gpu_route_batch(const struct xsknf_gpu_desc *descs, cons
 XSKNF_GPU_API int xsknf_gpu_route_host(const struct xsknf_gpu_desc *descs, const int32_t *verdicts, uint32_t n,
 		uint32_t num_interfaces, struct xsknf_gpu_desc *tx_descs, uint64_t *fill_addrs, uint32_t *order,
 		uint64_t *counts);
+
+/* ---- forwarding routed frames into their tx interface's UMEM ----------------
+ * The third part of the reference's batch loop (process_batch, src/xsknf.c:
+ * 548-584): when the destination interface has a UMEM of its own (rx_xsk->buffer
+ * != xsks[i].buffer, :563-571) every forwarded frame's bytes are copied into
+ * that UMEM at the same address before its descriptor goes into the tx ring;
+ * an interface that shares the rx UMEM gets the descriptors alone (:572-579).
+ * These calls do that copy for the tx lists xsknf_gpu_route_batch leaves, on
+ * the device or (the model the device is held to) on one CPU thread, with the
+ * same destination bytes and stats.
+ *
+ * tx_descs and counts are exactly what the router leaves: interface i's list is
+ * tx_descs[base_i .. base_i + counts[i]), base_i = counts[0] + ... + counts[i - 1];
+ * counts has num_interfaces + 1 words (the last, the drops, is not used).
+ * tx_umems and tx_umem_sizes are HOST arrays of num_interfaces entries, read
+ * before the call returns.  tx_umems[i] NULL or equal to rx_umem: interface i
+ * shares the rx UMEM, and its entries are not copied, not range-checked and not
+ * counted.  For every other interface each entry {addr, len} copies exactly len
+ * bytes from rx_umem + off to tx_umems[i] + off, with
+ *   off = (addr & XSKNF_GPU_UNALIGNED_BUF_ADDR_MASK) + (addr >> 48),
+ * the runtime's addr_offset() (xsknf_rt.c dispose_multi).  The reference indexes
+ * both UMEMs with the untranslated `orig` (:565-566), which in unaligned mode
+ * carries the offset in its upper 16 bits and is a wild address; in aligned mode
+ * the two are the same.  We follow the runtime.
+ * An entry is copied only if off <= size && len <= size - off holds for both
+ * rx_umem_size and tx_umem_sizes[i]; otherwise it is skipped and counted in
+ * stats[2].  len == 0 is a copied frame of 0 bytes.  No byte of any destination
+ * UMEM outside [off, off + len) of a copied frame is written; the rx UMEM and
+ * tx_descs are only read.  The frames of a batch are distinct chunks, as
+ * everywhere in this header: two entries naming the same bytes write the same
+ * values twice.
+ *
+ * -EINVAL for both calls, before anything is read through the pointers:
+ * num_interfaces 0 or > 32; a NULL tx_umems or tx_umem_sizes; rx_umem or a
+ * non-NULL tx_umems[i] not 16-byte aligned; a non-NULL tx_umems[i] other than
+ * rx_umem whose [p, p + size) overlaps [rx_umem, rx_umem + rx_umem_size); two
+ * different non-NULL destination UMEMs that overlap each other (the same UMEM
+ * under two interfaces is fine); tx_descs not 16-byte aligned, counts or
+ * stats_dev not 8-byte aligned; and, with entries to look at, a NULL rx_umem,
+ * tx_descs, counts or stats_dev. */
+/* stats: [0] frames copied, [1] bytes copied, [2] frames skipped (out of range) */
+#define XSKNF_GPU_FORWARD_STATS 3
+
+/* On the current device, on `stream` (a hipStream_t; NULL: the default stream).
+ * rx_umem, the pointers in tx_umems, tx_descs, counts_dev and stats_dev are
+ * device memory.  The counts are read ON THE DEVICE, so a route with counts ==
+ * NULL and this call can be enqueued back to back with the route's workspace
+ * pointer as counts_dev and no host read-back between.  n is only an upper bound
+ * on the tx total -- the capacity of tx_descs, which sizes the grid; entries at
+ * or past the real total (or n) are never read.
+ * stats_dev (3 u64, required) is zeroed on the stream first and holds the stats
+ * once the stream gets there.  stats (HOST, 3 u64, may be NULL): given, the call
+ * waits for `stream` and fills it; NULL, the call only enqueues.
+ * n == 0 succeeds with nothing touched on the device (the device pointers may be
+ * NULL); n > 0 with no interface to copy for (all NULL or rx_umem) zeroes
+ * stats_dev and launches nothing.  A given stats is all 0 in both cases.
+ * -EIO on a HIP error, with xsknf_gpu_last_error() set. */
+XSKNF_GPU_API int xsknf_gpu_forward_frames(const uint8_t *rx_umem, uint64_t rx_umem_size,
+		uint8_t *const *tx_umems, const uint64_t *tx_umem_sizes, uint32_t num_interfaces,
+		const struct xsknf_gpu_desc *tx_descs, const uint64_t *counts_dev, uint32_t n,
+		uint64_t *stats_dev, uint64_t *stats, void *stream);
+/* The same on host arrays: one thread, a memcpy per entry, no GPU call.  The
+ * number of entries is the sum of counts[0 .. num_interfaces); stats may be
+ * NULL, and with no entry so may rx_umem, tx_descs and counts. */
+XSKNF_GPU_API int xsknf_gpu_forward_host(const uint8_t *rx_umem, uint64_t rx_umem_size,
+		uint8_t *const *tx_umems, const uint64_t *tx_umem_sizes, uint32_t num_interfaces,
+		const struct xsknf_gpu_desc *tx_descs, const uint64_t *counts, uint64_t *stats);
 
 /* Text of the last HIP error seen by this library, on any thread (a copy
  * private to the calling thread). */

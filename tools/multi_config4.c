@@ -5,7 +5,7 @@
  * links the CPU oracle (oracle/build/libcsum_oracle.so, pinned to the
  * reference's own function by tests/test_ref_pin.py) as the checker.
  *
- *   multi_config4 [frames (default 8388608)] [devices (default: all)] [--device-descs] [--route]
+ *   multi_config4 [frames (default 8388608)] [devices (default: all)] [--device-descs] [--route] [--forward]
  *
  * --device-descs (anywhere on the line): the descriptors are copied to device 0
  * once and both scatters go through xsknf_gpu_multi_scatter_dev, which plans on
@@ -18,6 +18,13 @@
  * the oracle's verdicts; the JSON line gains route_match and route_ms (one
  * warmed call with its counts read back, on the host's clock), and the exit
  * status covers route_match.
+ *
+ * --forward (implies --route): the routed tx list is then forwarded into a
+ * second UMEM on device 0 (xsknf_gpu_forward_frames: the interface's UMEM is
+ * not the rx UMEM, src/xsknf.c:563-571), and that UMEM, every byte, and the
+ * stats are compared with xsknf_gpu_forward_host over the host copies; the JSON
+ * line gains forward_match and forward_ms (one warmed call with its stats read
+ * back, on the host's clock), and the exit status covers forward_match.
  *
  * The batch: IMIX 64 / 570 / 1500 B frames (7:4:1, shuffled), one per 2 KiB
  * chunk at +256 (aligned mode), Eth / IPv4 / UDP headers, random payload, built
@@ -119,12 +126,49 @@ static void host_counters(const uint8_t *umem, uint64_t umem_size, const struct 
 	}
 }
 
+/* --forward: the routed tx list at dtx (device 0, its counts the first words of
+ * the router's workspace ws) forwarded from the UMEM at `umem` into a second,
+ * sentinel-filled UMEM; that UMEM and the stats against xsknf_gpu_forward_host
+ * over `ref` (the oracle's pass: what `umem` holds), wtx and want.  scratch_a and
+ * scratch_b are umem_size host bytes each.  *seconds: the second of two calls,
+ * its stats read back. */
+static int forward_check(const uint8_t *umem, uint64_t umem_size, const uint8_t *ref,
+			 const struct xsknf_gpu_desc *dtx, const void *ws, uint32_t n,
+			 const struct xsknf_gpu_desc *wtx, const uint64_t *want, uint8_t *scratch_a,
+			 uint8_t *scratch_b, double *seconds)
+{
+	uint8_t *dst = NULL;
+	uint64_t *dstats = NULL;
+	uint64_t got[XSKNF_GPU_FORWARD_STATS] = {~0ull, ~0ull, ~0ull}, hs[XSKNF_GPU_FORWARD_STATS];
+	HIP_OK(hipMalloc((void **)&dst, umem_size ? umem_size : 16));
+	HIP_OK(hipMalloc((void **)&dstats, sizeof(got)));
+	HIP_OK(hipMemset(dst, 0xA5, umem_size));
+	uint8_t *const tx_umems[1] = {dst};
+	const uint64_t tx_sizes[1] = {umem_size};
+	XS_OK(xsknf_gpu_forward_frames(umem, umem_size, tx_umems, tx_sizes, 1, dtx, ws, n, dstats, got, NULL));
+	const double t0 = now();
+	XS_OK(xsknf_gpu_forward_frames(umem, umem_size, tx_umems, tx_sizes, 1, dtx, ws, n, dstats, got, NULL));
+	*seconds = now() - t0;
+	HIP_OK(hipMemcpy(scratch_a, dst, umem_size, hipMemcpyDeviceToHost));
+	memset(scratch_b, 0xA5, umem_size);
+	uint8_t *const host_umems[1] = {scratch_b};
+	XS_OK(xsknf_gpu_forward_host(ref, umem_size, host_umems, tx_sizes, 1, wtx, want, hs));
+	const int ok = !memcmp(got, hs, sizeof(got)) && hs[0] == want[0] && hs[2] == 0 &&
+		       !memcmp(scratch_a, scratch_b, umem_size);
+	HIP_OK(hipFree(dst));
+	HIP_OK(hipFree(dstats));
+	return ok;
+}
+
 /* --route: the verdicts at `verdicts` (device 0, beside the descriptors at
  * ddescs) routed there, one interface as the pass above ran; every count and
  * every entry of the lists against xsknf_gpu_route_host over the oracle's
- * verdicts.  *seconds: the second of two calls, its counts read back. */
+ * verdicts.  *seconds: the second of two calls, its counts read back.  With
+ * forward_match, the lists then go through forward_check. */
 static int route_check(const struct xsknf_gpu_desc *ddescs, const int32_t *verdicts,
-		       const struct xsknf_gpu_desc *descs, const int32_t *ov, uint32_t n, double *seconds)
+		       const struct xsknf_gpu_desc *descs, const int32_t *ov, uint32_t n, double *seconds,
+		       const uint8_t *umem, uint64_t umem_size, const uint8_t *ref, uint8_t *scratch_a,
+		       uint8_t *scratch_b, int *forward_match, double *forward_seconds)
 {
 	const uint32_t nif = 1;
 	const size_t m = n ? n : 1;
@@ -156,6 +200,9 @@ static int route_check(const struct xsknf_gpu_desc *ddescs, const int32_t *verdi
 	for (uint64_t i = 0; ok && i < want[1]; i++)
 		ok = fill[i] == wfill[i];
 	ok = ok && !memcmp(order, worder, sizeof(uint32_t) * n);
+	if (forward_match)
+		*forward_match = n == 0 || forward_check(umem, umem_size, ref, dtx, ws, n, wtx, want, scratch_a,
+							 scratch_b, forward_seconds);
 	HIP_OK(hipFree(dtx));
 	HIP_OK(hipFree(dfill));
 	HIP_OK(hipFree(dorder));
@@ -166,12 +213,14 @@ static int route_check(const struct xsknf_gpu_desc *ddescs, const int32_t *verdi
 
 int main(int argc, char **argv)
 {
-	int dev_descs = 0, do_route = 0, nargs = 1;
+	int dev_descs = 0, do_route = 0, do_forward = 0, nargs = 1;
 	for (int a = 1; a < argc; a++) {   /* the option out of the way of the positional arguments */
 		if (!strcmp(argv[a], "--device-descs"))
 			dev_descs = 1;
 		else if (!strcmp(argv[a], "--route"))
 			do_route = 1;
+		else if (!strcmp(argv[a], "--forward"))
+			do_route = do_forward = 1;
 		else
 			argv[nargs++] = argv[a];
 	}
@@ -270,10 +319,11 @@ int main(int argc, char **argv)
 	}
 	XS_OK(xsknf_gpu_multi_destroy(m));
 	HIP_OK(hipSetDevice(0));
-	int route_match = 1;
-	double t_route = 0;
-	if (do_route)
-		route_match = route_check(ddescs, verdicts, descs, ov, (uint32_t)n, &t_route);
+	int route_match = 1, forward_match = 1;
+	double t_route = 0, t_forward = 0;
+	if (do_route)   /* (host and back are free here: the batch is on the device, the read-back follows) */
+		route_match = route_check(ddescs, verdicts, descs, ov, (uint32_t)n, &t_route, umem, umem_size, ref,
+					  back, host, do_forward ? &forward_match : NULL, &t_forward);
 	HIP_OK(hipMemcpy(back, umem, umem_size, hipMemcpyDeviceToHost));
 	HIP_OK(hipMemcpy(gv, verdicts, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
 	const int umem_match = !memcmp(back, ref, umem_size);
@@ -290,10 +340,13 @@ int main(int argc, char **argv)
 		       (t_plan_span + t_plan_pack) * 1e3, t_plan_span * 1e3, t_plan_pack * 1e3);
 	if (do_route)
 		printf(", \"route_match\": %s, \"route_ms\": %.3f", route_match ? "true" : "false", t_route * 1e3);
+	if (do_forward)
+		printf(", \"forward_match\": %s, \"forward_ms\": %.3f", forward_match ? "true" : "false",
+		       t_forward * 1e3);
 	printf("}\n");
 	if (ddescs)
 		HIP_OK(hipFree(ddescs));
 	HIP_OK(hipFree(umem));
 	HIP_OK(hipFree(verdicts));
-	return counters_match && umem_match && verdicts_match && route_match ? 0 : 1;
+	return counters_match && umem_match && verdicts_match && route_match && forward_match ? 0 : 1;
 }

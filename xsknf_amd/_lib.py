@@ -55,9 +55,12 @@ EXPORTED_SYMBOLS = (
     "xsknf_gpu_route_workspace",
     "xsknf_gpu_route_batch",
     "xsknf_gpu_route_host",
+    "xsknf_gpu_forward_frames",
+    "xsknf_gpu_forward_host",
 )
 
 ROUTE_MAX_INTERFACES = 32   # XSKNF_GPU_ROUTE_MAX_INTERFACES
+FORWARD_STATS = 3           # XSKNF_GPU_FORWARD_STATS
 
 MULTI_COUNTERS = 6   # XSKNF_GPU_MULTI_COUNTERS
 
@@ -260,6 +263,10 @@ def load() -> ctypes.CDLL:
     lib.xsknf_gpu_route_batch.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, vp, vp, u64, vp]
     lib.xsknf_gpu_route_host.restype = ctypes.c_int
     lib.xsknf_gpu_route_host.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, vp]
+    lib.xsknf_gpu_forward_frames.restype = ctypes.c_int
+    lib.xsknf_gpu_forward_frames.argtypes = [vp, u64, vp, vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp, vp, vp]
+    lib.xsknf_gpu_forward_host.restype = ctypes.c_int
+    lib.xsknf_gpu_forward_host.argtypes = [vp, u64, vp, vp, ctypes.c_uint32, vp, vp, vp]
     lib.xsknf_gpu_pool_guard_trips.restype = ctypes.c_int
     lib.xsknf_gpu_pool_guard_trips.argtypes = [ctypes.POINTER(ctypes.c_uint32), ctypes.c_int]
     _lib = lib

@@ -174,6 +174,17 @@ class Checksummer:
 
         return _route.route_batch(descs, verdicts, self.num_interfaces, order=order)
 
+    def forward(self, rx_umem, tx_umems, tx_descs, counts, *, n=None):
+        """The copy that ends the batch loop (src/xsknf.c:563-571), on the
+        device: every frame of route()'s tx lists whose interface has a UMEM of
+        its own (tx_umems[i], a uint8 device tensor; None: it shares rx_umem) is
+        copied there at the same offset (route.forward_frames: the stats)."""
+        from . import route as _route
+
+        if len(tx_umems) != self.num_interfaces:
+            raise ValueError("one UMEM (or None) per interface")
+        return _route.forward_frames(rx_umem, tx_umems, tx_descs, counts, n=n)
+
 
 class HostPath:
     """The batch hook with the UMEM in host memory (include/xsknf_gpu.h
