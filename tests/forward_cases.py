@@ -2,9 +2,13 @@
 independent numpy model of the frame forward (include/xsknf_gpu.h, "forwarding
 routed frames"), 16-byte aligned arrays, frame layouts that mix the lengths and
 every address mod 16, and the comparison of destination UMEMs with the model --
-every byte, the sentinels outside the frames included."""
+every byte, the sentinels outside the frames included.  For the batches past
+one sweep of the device forward's grid: the sweep read from the code, packed
+frames built vectorised, the model as a flat scatter, and the counts a capacity
+below the tx total leaves."""
 import numpy as np
 
+from tests.route_cases import code_constant, code_match
 from xsknf_amd import frames
 
 SENTINEL8 = 0xA5                       # every destination byte before a call
@@ -62,6 +66,78 @@ def mixed_frames(n, lens=LENS, unaligned=True):
     return out, max(chunk, 1) * CHUNK
 
 
+PACKED_LENS = [0, 1, 2, 15, 16, 17, 31, 32, 33, 47, 64]
+PACKED_LONG, PACKED_EVERY = 4200, 4099     # a frame of more than 64 * kUnroll chunks, every 4099th
+
+
+def grid_sweep():
+    """G: the entries one sweep of forward_frames' persistent grid takes, from
+    the code: kMaxBlocks blocks of kThreads / 64 waves, a 64-entry tile each.
+    Also holds the code to what the long tests lean on: the grid is capped at
+    kMaxBlocks, a wave strides by the whole grid's waves, and PACKED_LONG bytes
+    are more chunks than one trip of the chunk loop moves."""
+    h = "kernel_forward.h"
+    blocks = code_constant(h, r"constexpr uint32_t kMaxBlocks = (\d+);")
+    threads = code_constant(h, r"constexpr int kThreads = (\d+);")
+    wave = code_constant(h, r"constexpr int kWaves = kThreads / (\d+);")
+    tile = code_constant(h, r"const uint64_t e = t \* (\d+) \+ lane;")
+    assert wave == 64 and tile == 64
+    code_match(h, r"t \+= gridDim\.x \* static_cast<uint64_t>\(kWaves\)")
+    code_match("forward_device.hip", r"want < kMaxBlocks \? want : kMaxBlocks")
+    unroll = code_constant(h, r"constexpr int kUnroll = (\d+);")
+    code_match(h, r"k0 \+= 64ull \* kUnroll")
+    assert PACKED_LONG > 64 * unroll * 16
+    return blocks * (threads // wave) * tile
+
+
+def packed_frames(n):
+    """(n descriptors, the rx UMEM's size) for the batches past one sweep of the
+    forward's grid: the lengths of PACKED_LENS in turn, every PACKED_EVERY-th
+    frame PACKED_LONG bytes; frame e + 1 starts e % 3 bytes after frame e's end,
+    so neighbours share 16-byte chunks and the starts step through every address
+    mod 16; every other address as base | offset << 48.  About 26 bytes a frame."""
+    e = np.arange(n, dtype=np.uint64)
+    ln = np.array(PACKED_LENS, dtype=np.uint64)[e % np.uint64(len(PACKED_LENS))]
+    ln[PACKED_EVERY - 1::PACKED_EVERY] = PACKED_LONG
+    step = ln + e % np.uint64(3)
+    start = np.cumsum(step, dtype=np.uint64) - step + np.uint64(5)
+    delta = np.where((e % np.uint64(2) == 1) & (start >= 300), np.uint64(256) + e % np.uint64(7), np.uint64(0))
+    d = aligned_descs(n)
+    d["addr"] = (start - delta) | (delta << np.uint64(SHIFT))
+    d["len"] = ln.astype(np.uint32)
+    d["options"] = 7
+    return d, (int((start + ln).max()) + 64 & ~15) if n else 64
+
+
+def offsets_of(addr):
+    """offset_of over an array of addresses."""
+    a = np.asarray(addr, dtype=np.uint64)
+    return (a & np.uint64(MASK)) + (a >> np.uint64(SHIFT))
+
+
+def past_sweep(tx, counts, dst_sizes, rx_size, sweep):
+    """What a routed batch holds at tx entries of index >= sweep (taken by a
+    wave's second or later tile) that the forward copies: (the set of start
+    addresses mod 16, the set of lengths, the number of entries)."""
+    nif = len(dst_sizes)
+    owner = np.repeat(np.arange(nif), counts[:nif])
+    lim = np.array([0 if s is None else min(s, rx_size) for s in dst_sizes], dtype=np.uint64)[owner]
+    off, ln = offsets_of(tx["addr"][:owner.size]), tx["len"][:owner.size].astype(np.uint64)
+    live = (off + ln <= lim) & (lim > 0)
+    live[:sweep] = False
+    return set((off[live] % np.uint64(16)).tolist()), set(ln[live].tolist()), int(live.sum())
+
+
+def clip_counts(counts, nif, cap):
+    """The per-interface counts of the first `cap` tx entries: what
+    xsknf_gpu_forward_frames looks at when its capacity n is below the tx total."""
+    out, left = [], int(cap)
+    for c in counts[:nif]:
+        out.append(min(int(c), left))
+        left -= out[-1]
+    return out + [0]
+
+
 def lists(per_if):
     """per_if: one list of (addr, len) per interface -> (tx_descs, counts with
     the drop count 0 after them).  options 0, as the router writes them."""
@@ -95,6 +171,30 @@ def model(rx, dst_sizes, tx, counts):
                     st[1] += ln
                 else:
                     st[2] += 1
+        base += c
+    return dsts, st
+
+
+def model_flat(rx, dst_sizes, tx, counts, block=1 << 16):
+    """model() for long lists: the copied entries' bytes by one flat index
+    scatter per `block` entries instead of a Python loop per entry.  (model()
+    stays the definition; tests/test_forward.py holds this one to it.)"""
+    dsts = [None if s is None else np.full(s, SENTINEL8, dtype=np.uint8) for s in dst_sizes]
+    off, ln = offsets_of(tx["addr"]), tx["len"].astype(np.uint64)      # (off < 2^49, len < 2^32: no wrap below)
+    st, base = [0, 0, 0], 0
+    for i, d in enumerate(dsts):
+        c = int(counts[i])
+        if d is not None:
+            o, l = off[base:base + c], ln[base:base + c]
+            ok = (o + l <= np.uint64(rx.size)) & (o + l <= np.uint64(d.size))
+            st[0] += int(ok.sum())
+            st[1] += int(l[ok].sum())
+            st[2] += c - int(ok.sum())
+            o, l = o[ok].astype(np.int64), l[ok].astype(np.int64)
+            for s in range(0, o.size, block):
+                ob, lb = o[s:s + block], l[s:s + block]
+                idx = np.repeat(ob - (np.cumsum(lb) - lb), lb) + np.arange(int(lb.sum()))
+                d[idx] = rx[idx]
         base += c
     return dsts, st
 

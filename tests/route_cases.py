@@ -1,8 +1,13 @@
 """What tests/test_route.py (CPU) and tests/test_gpu_route.py share: an
 independent numpy model of the routing (include/xsknf_gpu.h, "routing a
 checksummed batch"), the verdict patterns, random descriptors and the comparison
-of a result with the model -- sentinels past the totals included."""
+of a result with the model -- sentinels past the totals included.  Also the
+constants the long-batch tests read from the kernels' sources (the router's and
+the planner's scans share block_scan.h, so tests/test_gpu_plan_dev.py and
+tests/test_plan_dev.py take them, and the planner's long descriptors, from here)."""
 import ctypes
+import os
+import re
 
 import numpy as np
 
@@ -12,6 +17,47 @@ INT32_MIN, INT32_MAX = -(1 << 31), (1 << 31) - 1
 SENTINEL8 = 0xA5                       # every output byte before a call
 SENTINEL32 = 0xA5A5A5A5
 SENTINEL64 = 0xA5A5A5A5A5A5A5A5
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "xsknf_amd", "csrc")
+
+
+def code_match(header, pattern):
+    """re.search(pattern) in xsknf_amd/csrc/<header>.  A pattern the code no
+    longer holds is an error: a size taken from the code must move with the code
+    or fail, never quietly become a stale number."""
+    src = open(os.path.join(CSRC, header)).read()
+    m = re.search(pattern, src)
+    assert m, f"{header} no longer matches {pattern!r}: re-derive the test sizes that were read from it"
+    return m
+
+
+def code_constant(header, pattern):
+    """The integer the one group of `pattern` names in xsknf_amd/csrc/<header>."""
+    return int(code_match(header, pattern).group(1))
+
+
+def scan_trip():
+    """S: the tile counts one trip of the scan loops takes (route_scan_counts,
+    plan_scan_totals): scan::kThreads of block_scan.h, which both kernel files
+    pin to their own kThreads and step their scan loops by."""
+    s = code_constant("block_scan.h", r"namespace scan \{\s*constexpr int kThreads = (\d+);")
+    for header in ("kernel_route.h", "kernel_plan.h"):
+        code_match(header, r"static_assert\(scan::kThreads == kThreads,")
+        code_match(header, r"for \(uint64_t i0 = 0; i0 < nb; i0 \+= kThreads\) \{")
+        assert code_constant(header, r"constexpr int kThreads = (\d+);") == s
+    return s
+
+
+def tile_of(header):
+    """T: frames per block, kThreads * kPerThread of kernel_route.h / kernel_plan.h."""
+    code_match(header, r"kTile = kThreads \* kPerThread;")
+    return code_constant(header, r"constexpr int kThreads = (\d+);") * code_constant(
+        header, r"constexpr int kPerThread = (\d+);")
+
+
+def long_sizes(s, t):
+    """The smallest batches past one scan trip: a second trip whose only tile
+    holds one frame; three trips, the last partial, n no multiple of 64."""
+    return [s * t + 1, 2 * s * t + 3 * t + 77]
 
 
 def bins_of(verdicts, nif):
@@ -47,12 +93,36 @@ def random_descs(n, seed):
 
 PATTERNS = ["all-drop", "all-one", "alternating", "one-absent", "long-runs", "uniform", "stray", "cycle",
             "tile-then-none"]
+# for the batches past one scan trip: tile-then-none leaves a bin empty in every
+# tile of the later trips, late-only one whose tile prefixes are all carry
+LONG_PATTERNS = ["uniform", "cycle", "tile-then-none", "late-only"]
+PLAN_LENS = [0, 1, 64, 570, 1500, 17, 128]
 
 
-def verdicts(pattern, n, nif, seed=7, tile=2048):
+def plan_descs(n):
+    """(n descriptors, UMEM size) for the planner's long batches, with no UMEM
+    bytes behind them (the planner reads addresses and lengths alone): the
+    lengths of PLAN_LENS in turn, frame f + 1 starting f % 16 bytes after frame
+    f's end (7 lengths against 16 gaps: the starts step through every address
+    mod 16 against every length), every other address as base | offset << 48,
+    options all different."""
+    f = np.arange(n, dtype=np.uint64)
+    ln = np.array(PLAN_LENS, dtype=np.uint64)[f % np.uint64(len(PLAN_LENS))]
+    step = ln + f % np.uint64(16)
+    start = np.cumsum(step, dtype=np.uint64) - step + np.uint64(3)
+    delta = np.where((f % np.uint64(2) == 1) & (start >= 300), np.uint64(256) + f % np.uint64(7), np.uint64(0))
+    d = np.zeros(n, dtype=frames.DESC_DTYPE)
+    d["addr"] = (start - delta) | (delta << np.uint64(48))
+    d["len"] = ln.astype(np.uint32)
+    d["options"] = (f * np.uint64(2654435761) + np.uint64(1)).astype(np.uint32)
+    return d, (int((start + ln).max()) + 15 & ~15) if n else 16
+
+
+def verdicts(pattern, n, nif, seed=7, tile=2048, trip=256):
     """n int32 verdicts.  cycle: -1, 0 .. nif-1 in turn (nif = 32: every run of
     64 frames holds all 33 bins).  tile-then-none: interface 0 for one tile,
-    then no frame of it."""
+    then no frame of it.  late-only: no frame of interface 0 in the first `trip`
+    tiles, then every third frame (the first of them included)."""
     rng = np.random.default_rng(seed)
     i = np.arange(n, dtype=np.int64)
     if pattern == "all-drop":
@@ -79,6 +149,11 @@ def verdicts(pattern, n, nif, seed=7, tile=2048):
         v = i % (nif + 1) - 1
     elif pattern == "tile-then-none":
         v = np.where(i < tile, 0, np.where(i % 3 == 0, -1, nif - 1 if nif > 1 else -1))
+    elif pattern == "late-only":
+        v = rng.integers(0, nif, n)        # the other bins, the drops among them, everywhere
+        v[v == 0] = -1
+        late = trip * tile
+        v[late::3] = 0
     else:
         raise ValueError(pattern)
     return np.ascontiguousarray(v.astype(np.int32))

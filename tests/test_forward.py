@@ -176,6 +176,86 @@ def test_forward_host_equals_the_numpy_model(nif):
     assert again[0] == stats[0] - counts[0] and again[2] == stats[2]       # (interface 0's frames were all in range)
 
 
+def test_the_flat_model_is_the_model():
+    """FC.model_flat, the model for the long lists, against FC.model's per-entry
+    loop on the mixed frames and the UMEM edges, in blocks of 7 entries."""
+    fr, size = FC.mixed_frames(13 * 16)
+    rx = FC.rx_bytes(size, seed=9)
+    edges = [(size - 100, 100), (size - 100, 101), (size, 0), (size + 1, 0), (64, 0xFFFFFFFF), (1 << 47, 1),
+             ((size - 300) | (200 << 48), 100), ((size - 300) | (201 << 48), 100), ((1 << 64) - 1, 0xFFFFFFFF)]
+    for nif in NIFS:
+        tx, counts = FC.lists(FC.deal(fr + edges, nif))
+        sizes = FC.umem_sizes(nif, size)
+        want, wstats = FC.model(rx, sizes, tx, counts)
+        for block in (7, 1 << 16):
+            got, stats = FC.model_flat(rx, sizes, tx, counts, block=block)
+            assert stats == wstats
+            FC.same_umems(got, want, f"flat model nif={nif}")
+
+
+def test_forward_host_equals_the_model_past_one_grid_sweep():
+    """The largest batch the device forward is held to forward_host at
+    (tests/test_gpu_forward.py: more than two sweeps of its grid), as routed
+    there -- dealt to 3 interfaces in turn: own and full-size, shared, own and
+    smaller -- and the conditions that batch must meet for the device test to
+    mean what it says."""
+    g = FC.grid_sweep()
+    n = 2 * g + 64 * 5 + 3
+    d, size = FC.packed_frames(n)
+    off = FC.offsets_of(d["addr"])
+    assert np.all(off[1:] >= off[:-1] + d["len"][:-1]) and int(off[-1]) + int(d["len"][-1]) <= size
+    assert (off[1:] < off[:-1] + d["len"][:-1] + np.uint64(16)).all()             # neighbours share chunks
+    assert (d["addr"][1::2][100:] >> np.uint64(48)).all() and not (d["addr"][::2] >> np.uint64(48)).any()
+    rx = FC.rx_bytes(size, seed=44)
+    sizes = FC.umem_sizes(3, size)
+    assert sizes[0] == size and sizes[1] is None and sizes[2] < size
+    v = (np.arange(n) % 3).astype(np.int32)
+    tx, _, _, counts = route.route_host(d, v, 3)
+    assert sum(counts[:3]) == n > 2 * g and counts[0] + counts[1] > g        # interface 2's list lies past G
+    res, lens, live = FC.past_sweep(tx, counts, sizes, size, g)
+    assert res == set(range(16)) and lens == set(FC.PACKED_LENS) | {FC.PACKED_LONG} and live > 1000
+    txa = FC.aligned_descs(n)
+    txa[:] = tx
+    want, wstats = FC.model_flat(rx, sizes, txa, counts)
+    got = FC.fresh(sizes)
+    assert route.forward_host(rx, got, txa, counts) == wstats and wstats[0] > 0 and wstats[2] > 0
+    FC.same_umems(got, want, "past one grid sweep")
+    # the smaller batch: one entry past the sweep
+    v1 = v[:g + 1]
+    _, _, _, c1 = route.route_host(d[:g + 1], v1, 3)
+    assert sum(c1[:3]) == g + 1
+    # cycle verdicts (a quarter dropped) over the larger batch still fill more than one sweep
+    vc = RC.verdicts("cycle", n, 3)
+    txc, _, _, cc = route.route_host(d, vc, 3)
+    assert g < sum(cc[:3]) < n
+    res, lens, live = FC.past_sweep(txc, cc, [None, sizes[2], size], size, g)
+    assert res == set(range(16)) and lens == set(FC.PACKED_LENS) | {FC.PACKED_LONG} and live > 1000
+
+
+@pytest.mark.parametrize("cap", [0, 1, 64, 86, 87, 200, 256, 257, 300])
+def test_clipped_counts_against_the_model(cap):
+    """FC.clip_counts -- what a capacity below the tx total leaves of each
+    interface's list (tests/test_gpu_forward.py) -- against a count of the
+    first `cap` entries' owners; forward_host over the clipped counts is the
+    model's over them, and the frames of the entries at or past `cap` keep their
+    sentinels."""
+    fr, size = FC.mixed_frames(257)
+    rx = FC.rx_bytes(size, seed=41)
+    tx, counts = FC.lists(FC.deal(fr, 3))
+    owner = np.repeat(np.arange(3), counts[:3])
+    clipped = FC.clip_counts(counts, 3, cap)
+    assert clipped == [int((owner[:cap] == i).sum()) for i in range(3)] + [0]
+    sizes = [size, None, size]
+    stats = _host_vs_model(rx, sizes, tx, clipped, f"cap={cap}")
+    assert stats[0] == int((owner[:cap] != 1).sum()) and stats[2] == 0
+    got = FC.fresh(sizes)
+    route.forward_host(rx, got, tx, clipped)
+    for j in range(min(cap, 257), 257):
+        if owner[j] != 1:
+            off, ln = FC.offset_of(tx["addr"][j]), int(tx["len"][j])
+            assert np.all(got[owner[j]][off:off + ln] == FC.SENTINEL8)
+
+
 def test_edges_of_the_umems():
     """A frame ending at the last byte of both UMEMs; one byte past the end of
     the rx UMEM; one byte past the end of a smaller destination; a length of

@@ -6,7 +6,9 @@ kernel_forward.h).
   every byte of every destination UMEM (the sentinels outside the frames
   included), the unchanged rx UMEM and the three stats.  (tests/test_forward.py
   holds forward_host to an independent model on the CPU.)  The lists come from a
-  real xsknf_gpu_route_batch on the device.
+  real xsknf_gpu_route_batch on the device.  Sizes: around the wave and the
+  block, past one and two sweeps of the persistent grid (G read from the code),
+  and a capacity below the tx total.
 * From the hot path: process_batch, route, forward, against the reference's
   checksummed bytes.
 """
@@ -56,15 +58,19 @@ class DevForward:
     """A routed batch forwarded on the device: xsknf_gpu_route_batch (enqueue
     only: its counts stay in the workspace) and xsknf_gpu_forward_frames, back to
     back on the current stream, into sentinel-filled destination UMEMs.
-    dst_sizes[i]: bytes of interface i's own UMEM, None (NULL) or "rx"."""
+    dst_sizes[i]: bytes of interface i's own UMEM, None (NULL) or "rx".
+    cap: the capacity the forward is told, where it is to be BELOW the tx total
+    (the buffer still holds all n + extra entries, the routed lists whole)."""
 
-    def __init__(self, dev, rx, d, v, dst_sizes, sync=True, extra=0):
+    def __init__(self, dev, rx, d, v, dst_sizes, sync=True, extra=0, cap=None):
         n, nif = int(d.shape[0]), len(dst_sizes)
         self.nif, self.n = nif, n
         self.rx = _to_dev(rx, dev)
         self.dd, self.dv = _to_dev(d, dev), _to_dev(v, dev)
-        cap = n + extra                  # entries past the tx total keep wild descriptors (0xA5...)
-        self.tx = torch.full((max(cap, 1) * 16,), RC.SENTINEL8, dtype=torch.uint8, device=dev)
+        held = n + extra                 # entries past the tx total keep wild descriptors (0xA5...)
+        self.tx = torch.full((max(held, 1) * 16,), RC.SENTINEL8, dtype=torch.uint8, device=dev)
+        cap = held if cap is None else cap
+        assert cap <= held
         self.fill = torch.full((max(n, 1) * 8,), RC.SENTINEL8, dtype=torch.uint8, device=dev)
         self.ws = torch.zeros(route.route_workspace(n, nif), dtype=torch.uint8, device=dev)
         self.dsts = [torch.full((s,), FC.SENTINEL8, dtype=torch.uint8, device=dev) if isinstance(s, int) else None
@@ -91,12 +97,16 @@ class DevForward:
         return [None if t is None else t.cpu().numpy() for t in self.dsts], stats
 
 
-def _same_as_host(fwd, rx, d, v, dst_sizes, what):
+def _same_as_host(fwd, rx, d, v, dst_sizes, what, cap=None):
     """The device's destinations and stats == xsknf_gpu_forward_host's over
-    route_host's lists; rx UMEM, descriptors and lists unchanged."""
+    route_host's lists (cap: over the first `cap` entries of them); rx UMEM,
+    descriptors and lists unchanged."""
     nif = len(dst_sizes)
     got, stats = fwd.result()
     tx, _, _, counts = route.route_host(d, v, nif)
+    full = counts
+    if cap is not None:
+        counts = FC.clip_counts(counts, nif, cap)
     txa = FC.aligned_descs(tx.shape[0])
     txa[:] = tx
     rw = FC.aligned_u8(rx.size)
@@ -106,7 +116,7 @@ def _same_as_host(fwd, rx, d, v, dst_sizes, what):
     assert stats == wstats, what
     FC.same_umems(got, want, what)
     assert np.array_equal(fwd.rx.cpu().numpy(), rx), f"{what}: the rx UMEM changed"
-    ntx = sum(counts[:nif])
+    ntx = sum(full[:nif])
     assert np.array_equal(fwd.tx.cpu().numpy()[:16 * ntx].view(frames.DESC_DTYPE), tx[:ntx]), what
     assert np.all(fwd.tx.cpu().numpy()[16 * ntx:] == RC.SENTINEL8), what
     return stats
@@ -156,6 +166,95 @@ def test_capacity_larger_than_the_total(dev, batch):
         v = RC.verdicts("cycle", len(fr), nif)
         sizes = [rx.size] * nif
         _same_as_host(DevForward(dev, rx, d, v, sizes, extra=100), rx, d, v, sizes, f"extra nif={nif}")
+
+
+@pytest.mark.parametrize("cap", [200, 64])
+def test_capacity_smaller_than_the_total(dev, batch, cap):
+    """n below the tx total (257 entries in lists of 86, 86 and 85): the first
+    `cap` entries alone are forwarded and counted -- 200 cuts interface 2's list
+    inside a tile, 64 interface 0's -- and every byte of the frames of the
+    entries at or past `cap` keeps its sentinel, although the lists behind the
+    capacity hold real descriptors."""
+    fr, rx = batch
+    d = _descs(fr)
+    n, nif = len(fr), 3
+    v = (np.arange(n) % nif).astype(np.int32)
+    tx, _, _, counts = route.route_host(d, v, nif)
+    assert sum(counts[:nif]) == n > cap
+    owner = np.repeat(np.arange(nif), counts[:nif])
+    for sizes in (_sizes(nif, rx.size), [rx.size] * nif):
+        fwd = DevForward(dev, rx, d, v, sizes, cap=cap)
+        stats = _same_as_host(fwd, rx, d, v, sizes, f"cap={cap} {sizes}", cap=cap)
+        own = np.array([isinstance(s, int) for s in sizes])[owner]
+        assert stats[0] + stats[2] == int(own[:cap].sum()) and stats[0] > 0
+        got, _ = fwd.result()
+        for j in np.flatnonzero(own[cap:]) + cap:
+            off, ln = FC.offset_of(tx["addr"][j]), int(tx["len"][j])
+            assert np.all(got[owner[j]][off:off + ln] == FC.SENTINEL8), f"entry {j} >= cap {cap} was copied"
+
+
+G = FC.grid_sweep()               # entries per sweep of forward_frames' grid
+LONG_TOTALS = [G + 1, 2 * G + 64 * 5 + 3]
+
+
+def test_grid_sweep_is_read_from_the_code():
+    """G = kMaxBlocks * (kThreads / 64) * 64, the patterns FC.grid_sweep holds
+    the code to, and the long totals: one entry, and 5 tiles and 3 entries, past
+    whole sweeps."""
+    blocks = RC.code_constant("kernel_forward.h", r"kMaxBlocks = (\d+);")
+    threads = RC.code_constant("kernel_forward.h", r"constexpr int kThreads = (\d+);")
+    assert G == blocks * (threads // 64) * 64
+    assert LONG_TOTALS[0] == G + 1 and LONG_TOTALS[1] // G == 2 and LONG_TOTALS[1] % 64 == 3
+
+
+@pytest.fixture(scope="module")
+def packed():
+    """FC.packed_frames at the larger long total and its rx UMEM (about 27 MB).
+    Shared, never written."""
+    d, size = FC.packed_frames(LONG_TOTALS[-1])
+    d.setflags(write=False)
+    return d, FC.rx_bytes(size, seed=44)
+
+
+def _long_run(dev, packed, n, v, sizes, what):
+    """The first n packed frames (a prefix of the rx UMEM holds them all: the
+    UMEM is cut to it, so the smaller destination scales with the batch)."""
+    d, rx = packed
+    d = d[:n]
+    end = int((FC.offsets_of(d["addr"]) + d["len"]).max()) + 64 & ~15
+    return d, rx[:end], _same_as_host(DevForward(dev, rx[:end], d, v, sizes(end)), rx[:end], d, v, sizes(end), what)
+
+
+@pytest.mark.parametrize("n", LONG_TOTALS)
+def test_device_equals_forward_host_past_one_grid_sweep(dev, packed, n):
+    """A tx total above G (and above 2 G): the grid is capped at kMaxBlocks and
+    every wave takes a second (third) tile, rewriting its LDS rows, under a
+    64-bit tile index.  No drops, 3 interfaces in turn: own and full-size,
+    shared, own and smaller (its far frames skipped)."""
+    nif = 3
+    v = (np.arange(n) % nif).astype(np.int32)
+    d, rx, stats = _long_run(dev, packed, n, v, lambda size: FC.umem_sizes(nif, size), f"n={n}")
+    tx, _, _, counts = route.route_host(d, v, nif)
+    assert sum(counts[:nif]) == n > (1 if n == LONG_TOTALS[0] else 2) * G
+    assert stats[0] > 0 and stats[2] > 0 and stats[0] + stats[2] == counts[0] + counts[2]
+    if n > 2 * G:
+        assert counts[0] + counts[1] > G                          # interface 2's list lies wholly past G
+        res, lens, live = FC.past_sweep(tx, counts, FC.umem_sizes(nif, rx.size), rx.size, G)
+        assert res == set(range(16)) and lens == set(FC.PACKED_LENS) | {FC.PACKED_LONG} and live > 1000
+
+
+def test_cycle_verdicts_past_one_grid_sweep(dev, packed):
+    """Drops included (a quarter of the frames): the tx total still exceeds G.
+    Interface 0 shares the rx UMEM; the two with a UMEM of their own (smaller,
+    full-size) hold every entry past G."""
+    n, nif = LONG_TOTALS[-1], 3
+    v = RC.verdicts("cycle", n, nif)
+    d, rx, stats = _long_run(dev, packed, n, v, lambda size: [None, FC.umem_sizes(nif, size)[2], size], "cycle")
+    tx, _, _, counts = route.route_host(d, v, nif)
+    assert G < sum(counts[:nif]) < n and counts[0] < G < counts[0] + counts[1] + counts[2]
+    res, lens, live = FC.past_sweep(tx, counts, [None, FC.umem_sizes(nif, rx.size)[2], rx.size], rx.size, G)
+    assert res == set(range(16)) and lens == set(FC.PACKED_LENS) | {FC.PACKED_LONG} and live > 1000
+    assert stats[0] > 0 and stats[2] > 0
 
 
 def test_a_tile_of_zero_lengths_and_all_to_one_interface(dev):

@@ -3,7 +3,9 @@ xsknf_gpu_shard_plan_dev, xsknf_gpu_multi_scatter_dev; xsknf_amd/csrc/plan_devic
 
 * The planner against the host functions it restates -- xsknf_gpu_shard_plan,
   _shard_rebase and _shard_pack_plan on the same descriptors: every cut, span /
-  size, byte sum and every field of every output descriptor, for equality.
+  size, byte sum and every field of every output descriptor, for equality;
+  among the sizes, batches past one and two trips of the scan over the tile
+  totals (S tiles a trip, read from the code).
 * xsknf_gpu_multi_scatter_dev against the host scatters on the same object and
   batch (every shard's info, bytes and descriptors equal), then the results
   against the reference's pass over the whole batch.
@@ -16,6 +18,7 @@ import numpy as np
 import pytest
 
 from tests import oracles
+from tests import route_cases as RC
 from xsknf_amd import _lib, frames, multi
 
 pytestmark = pytest.mark.gpu
@@ -42,6 +45,8 @@ def _tile() -> int:
 T = _tile()
 SIZES = [0, 1, 2, 63, 64, 65, T - 1, T, T + 1, 2 * T + 1, 300001]
 SHARDS = [1, 2, 3, 8, 64]
+S = RC.scan_trip()                # block totals per trip of plan_scan_totals' loop
+LONG_SIZES = RC.long_sizes(S, T)  # two trips, the second of one frame; three trips, the last partial
 
 
 @pytest.fixture(scope="module")
@@ -161,6 +166,76 @@ def _mix(name, imix):
 
 MIXES = ["aligned-imix", "all-64", "eight-100", "tile-boundary", "zero-sprinkled", "all-zero", "every-37th-out",
          "huge-lens"]
+
+
+# ---- past one trip of plan_scan_totals' loop (more than S tiles) ----
+
+def test_scan_trip_is_read_from_the_code():
+    assert S == RC.code_constant("block_scan.h", r"constexpr int kThreads = (\d+);")
+    assert T == RC.tile_of("kernel_plan.h")
+    assert [-(-n // T) for n in LONG_SIZES] == [S + 1, 2 * S + 4]
+
+
+@pytest.fixture(scope="module")
+def long_plan():
+    """RC.plan_descs at the larger long size: (descriptors, UMEM size).  In
+    every scan trip every address mod 16 meets every length.  Shared, never
+    written."""
+    d, size = RC.plan_descs(LONG_SIZES[-1])
+    off = (d["addr"] & np.uint64((1 << 48) - 1)) + (d["addr"] >> np.uint64(48))
+    for lo in (0, S * T, 2 * S * T):
+        seen = set(zip((off[lo:lo + 4096] % np.uint64(16)).tolist(), d["len"][lo:lo + 4096].tolist()))
+        assert seen == {(r, ln) for r in range(16) for ln in RC.PLAN_LENS}
+    assert (d["addr"][1::2][200:] >> np.uint64(48)).all() and not (d["addr"][::2] >> np.uint64(48)).any()
+    d.setflags(write=False)
+    return d, size
+
+
+@pytest.mark.parametrize("nshards", [1, 3, 64])
+@pytest.mark.parametrize("n", LONG_SIZES)
+def test_planner_past_one_scan_trip(dev, long_plan, n, nshards):
+    """More than S tiles: plan_scan_totals carries the first trips' bytes and
+    slot bytes into the later tiles' prefixes, its binary search runs over more
+    than S entries, and plan_cuts / plan_pack read carry-ins a later trip wrote."""
+    descs, size = long_plan
+    ranges, _, _ = check_plan(dev, descs[:n].copy(), nshards, size)
+    if nshards == 64 and n == LONG_SIZES[-1]:
+        # cuts in both whole trips (the third, of 4 tiles, holds the batch's end: its carry is the total)
+        assert {hi // T // S for _, hi in ranges} == {0, 1, 2} and ranges[-2][1] // T // S == 1
+
+
+def _long_mix(name, long_plan):
+    descs, size = long_plan
+    if name == "trip-boundary":   # 2 * S * T equal frames: cuts on the boundary between the trips and on tile boundaries inside them
+        d = np.zeros(2 * S * T, dtype=frames.DESC_DTYPE)
+        d["addr"] = np.arange(d.size, dtype=np.uint64) * np.uint64(96) + np.uint64(5)
+        d["len"] = 90
+        return d, d.size * 96
+    if name == "first-trip-empty":   # all the bytes, and every cut, lie in later trips
+        d = descs.copy()
+        d["len"][:S * T] = 0
+        return d, size
+    if name == "every-37th-out":     # the slot prefix carries across the trips apart from the length prefix
+        d = descs.copy()
+        d["addr"][::37] += OUT
+        return d, size
+    raise ValueError(name)
+
+
+@pytest.mark.parametrize("mix,nshards", [("trip-boundary", 2), ("trip-boundary", 4), ("first-trip-empty", 3),
+                                         ("first-trip-empty", 64), ("every-37th-out", 3), ("every-37th-out", 64)])
+def test_planner_length_mixes_past_one_scan_trip(dev, long_plan, mix, nshards):
+    descs, size = _long_mix(mix, long_plan)
+    ranges, _, sizes = check_plan(dev, descs, nshards, size)
+    if mix == "trip-boundary":
+        assert [hi for _, hi in ranges] == [2 * S * T * (k + 1) // nshards for k in range(nshards)]
+        assert ranges[nshards // 2][0] == S * T
+    if mix == "first-trip-empty":
+        assert all(lo > S * T for lo, _ in ranges[1:])
+    if mix == "every-37th-out":
+        out = np.zeros(descs.size, dtype=bool)
+        out[::37] = True
+        assert all(out[lo:hi].any() for lo, hi in ranges) and all(s > 0 for s in sizes)
 
 
 @pytest.mark.parametrize("nshards", [1, 2, 3, 4, 8, 64])

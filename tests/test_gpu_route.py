@@ -4,7 +4,9 @@ xsknf_gpu_route_batch; xsknf_amd/csrc/route_device.hip, kernel_route.h).
 * The device against xsknf_gpu_route_host on the same arrays, for equality:
   the counts, every field of every list entry up to the totals, `order`, and
   the sentinels the buffers held past the totals.  (tests/test_route.py holds
-  route_host to an independent model on the CPU.)
+  route_host to an independent model on the CPU.)  Sizes: around the wave and
+  the tile, and past one and two trips of the scan over the tile counts (S
+  tiles a trip, read from the code).
 * From the hot path and after the multi-device round trip: the lists against the
   model applied to the reference's verdicts.
 """
@@ -44,6 +46,8 @@ def _tile() -> int:
 T = _tile()
 SIZES = [0, 1, 2, 63, 64, 65, T - 1, T, T + 1, 2 * T + 1, 300001]
 NIFS = [1, 2, 3, 32]
+S = RC.scan_trip()                # tile counts per trip of route_scan_counts' loop
+LONG_SIZES = RC.long_sizes(S, T)  # two trips, the second of one frame; three trips, the last partial
 
 
 @pytest.fixture(scope="module")
@@ -127,6 +131,52 @@ def test_device_equals_route_host(dev, descs, n, nif):
     if nif == 32 and n >= 64:
         v = RC.verdicts("cycle", n, nif)
         assert all(len(set(v[w:w + 64])) == 33 for w in range(0, n - 63, 64))
+
+
+def test_scan_trip_is_read_from_the_code():
+    """S is scan::kThreads, the step of the router's scan loop; the long sizes
+    are written in S and T, one frame and a partial trip past whole trips."""
+    assert S == RC.code_constant("block_scan.h", r"constexpr int kThreads = (\d+);")
+    assert T == RC.tile_of("kernel_route.h")
+    tiles = [-(-n // T) for n in LONG_SIZES]
+    assert tiles == [S + 1, 2 * S + 4] and LONG_SIZES[0] % T == 1 and LONG_SIZES[1] % 64
+
+
+@pytest.fixture(scope="module")
+def long_descs():
+    """Descriptors for the batches past one scan trip.  Shared, never written."""
+    d = RC.random_descs(LONG_SIZES[-1], seed=82)
+    d.setflags(write=False)
+    return d
+
+
+@pytest.mark.parametrize("nif", [1, 32])
+@pytest.mark.parametrize("n", LONG_SIZES)
+def test_device_equals_route_host_past_one_scan_trip(dev, long_descs, n, nif):
+    """More than S tiles: route_scan_counts takes a second (and third, partial)
+    trip of its loop, so the later tiles' prefixes carry the earlier trips'
+    totals, block_incl_scan reuses its LDS words and the header's counts are
+    sums over trips.  tile-then-none: a bin whose later trips are all zero;
+    late-only: interface 0's prefixes are nothing but carry."""
+    d = long_descs[:n]
+    dd = _to_dev(d, dev)
+    for pattern in RC.LONG_PATTERNS:
+        v = RC.verdicts(pattern, n, nif, seed=n + nif, tile=T, trip=S)
+        if pattern == "late-only":
+            assert not (RC.bins_of(v[:S * T], nif) == 0).any() and v[S * T] == 0
+        dv = _to_dev(v, dev)
+        _same_as_host(DevRoute(dev, dd, dv, n, nif).result(), d, v, nif, f"{pattern} n={n} nif={nif}")
+
+
+@pytest.mark.parametrize("n", LONG_SIZES)
+def test_counts_on_the_device_past_one_scan_trip(dev, long_descs, n):
+    """counts NULL: the header words of the workspace, each a carry over all
+    trips.  (uniform: whichever bin the last tile's frames fall in has a carry.)"""
+    d = long_descs[:n]
+    v = RC.verdicts("uniform", n, 3, seed=n)
+    r = DevRoute(dev, _to_dev(d, dev), _to_dev(v, dev), n, 3, sync=False)
+    assert r.counts is None
+    _same_as_host(r.result(), d, v, 3, f"counts NULL n={n}")
 
 
 @pytest.mark.parametrize("nif", [1, 3, 32])

@@ -139,6 +139,28 @@ def test_route_host_equals_the_numpy_model(pattern, nif):
         assert (RC.bins_of(v, nif) == 1).sum() == (v == -1).sum()        # the strays sent
 
 
+def test_route_host_equals_the_numpy_model_past_one_scan_trip():
+    """The largest batch the device router is held to route_host at
+    (tests/test_gpu_route.py: three trips of its scan loop), interface 0 only in
+    the later trips, 32 interfaces."""
+    s, t = RC.scan_trip(), RC.tile_of("kernel_route.h")
+    n = RC.long_sizes(s, t)[-1]
+    assert n > 2 * s * t and n % 64
+    d = RC.random_descs(n, seed=82)
+    v = RC.verdicts("late-only", n, 32, seed=n, tile=t, trip=s)
+    assert not (v[:s * t] == 0).any() and (v[s * t::3] == 0).all()
+    RC.same_as(RC.host_route_raw(d, v, 32), RC.model(d, v, 32), n, f"late-only n={n}")
+
+
+def test_late_only_at_small_sizes_has_no_frame_of_interface_0():
+    for nif in NIFS:
+        v = RC.verdicts("late-only", 5000, nif, seed=3)
+        assert not (RC.bins_of(v, nif) == 0).any()
+        assert set(RC.bins_of(v, nif)) == set(range(1, nif + 1))
+        v = RC.verdicts("late-only", 5000, nif, seed=3, tile=100, trip=20)
+        assert np.array_equal(np.flatnonzero(RC.bins_of(v, nif) == 0), np.arange(2000, 5000, 3))
+
+
 def test_the_python_wrapper_returns_the_same_lists():
     d = RC.random_descs(5000, 3)
     v = RC.verdicts("stray", 5000, 3)
