@@ -153,12 +153,21 @@ def deal(frames_, nif):
     return [frames_[i::nif] for i in range(nif)]
 
 
-def model(rx, dst_sizes, tx, counts):
+def _initial(dst_sizes, init):
+    """The destinations before a forward: sentinel-filled, or copies of `init`
+    (one array of dst_sizes[i] bytes per interface with a UMEM of its own)."""
+    if init is None:
+        return [None if s is None else np.full(s, SENTINEL8, dtype=np.uint8) for s in dst_sizes]
+    assert all((a is None) == (s is None) and (s is None or a.size == s) for a, s in zip(init, dst_sizes))
+    return [None if a is None else np.array(a, dtype=np.uint8) for a in init]
+
+
+def model(rx, dst_sizes, tx, counts, init=None):
     """The header's contract by per-entry slice assignment.  dst_sizes[i]: the
     size of interface i's own UMEM, or None where it shares the rx UMEM.
-    Returns (sentinel-filled destinations with the frames in them, or None;
-    stats)."""
-    dsts = [None if s is None else np.full(s, SENTINEL8, dtype=np.uint8) for s in dst_sizes]
+    Returns (the destinations -- sentinel-filled, or as `init` gives them --
+    with the frames in them, or None; stats)."""
+    dsts = _initial(dst_sizes, init)
     st, base = [0, 0, 0], 0
     for i, d in enumerate(dsts):
         c = int(counts[i])
@@ -175,11 +184,11 @@ def model(rx, dst_sizes, tx, counts):
     return dsts, st
 
 
-def model_flat(rx, dst_sizes, tx, counts, block=1 << 16):
+def model_flat(rx, dst_sizes, tx, counts, block=1 << 16, init=None):
     """model() for long lists: the copied entries' bytes by one flat index
     scatter per `block` entries instead of a Python loop per entry.  (model()
     stays the definition; tests/test_forward.py holds this one to it.)"""
-    dsts = [None if s is None else np.full(s, SENTINEL8, dtype=np.uint8) for s in dst_sizes]
+    dsts = _initial(dst_sizes, init)
     off, ln = offsets_of(tx["addr"]), tx["len"].astype(np.uint64)      # (off < 2^49, len < 2^32: no wrap below)
     st, base = [0, 0, 0], 0
     for i, d in enumerate(dsts):

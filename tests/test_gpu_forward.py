@@ -60,9 +60,11 @@ class DevForward:
     back on the current stream, into sentinel-filled destination UMEMs.
     dst_sizes[i]: bytes of interface i's own UMEM, None (NULL) or "rx".
     cap: the capacity the forward is told, where it is to be BELOW the tx total
-    (the buffer still holds all n + extra entries, the routed lists whole)."""
+    (the buffer still holds all n + extra entries, the routed lists whole).
+    fill: the destinations' bytes before the call, one array per interface with
+    a UMEM of its own (default: the sentinel everywhere)."""
 
-    def __init__(self, dev, rx, d, v, dst_sizes, sync=True, extra=0, cap=None):
+    def __init__(self, dev, rx, d, v, dst_sizes, sync=True, extra=0, cap=None, fill=None):
         n, nif = int(d.shape[0]), len(dst_sizes)
         self.nif, self.n = nif, n
         self.rx = _to_dev(rx, dev)
@@ -75,6 +77,11 @@ class DevForward:
         self.ws = torch.zeros(route.route_workspace(n, nif), dtype=torch.uint8, device=dev)
         self.dsts = [torch.full((s,), FC.SENTINEL8, dtype=torch.uint8, device=dev) if isinstance(s, int) else None
                      for s in dst_sizes]
+        if fill is not None:
+            for t, a in zip(self.dsts, fill):
+                assert (t is None) == (a is None)
+                if t is not None:
+                    t.copy_(torch.from_numpy(np.ascontiguousarray(a)))
         self.stats_dev = torch.full((3,), -1, dtype=torch.int64, device=dev)
         ptrs = [self.rx.data_ptr() if s == "rx" else (0 if t is None else t.data_ptr())
                 for s, t in zip(dst_sizes, self.dsts)]
