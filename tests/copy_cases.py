@@ -1,7 +1,7 @@
 """What tests/test_copy_sweep.py (CPU) and tests/test_gpu_copy_sweep.py share: the
 directed batches of tests/sweep_cases.py turned on the kernels that move frames
 around the checksum pass -- forward_frames (kernel_forward.h), pack_frames,
-apply_records and shard_counters (multi.hip), scatter_checks (kernel_scatter.h).
+apply_records and shard_counters (kernel_pack.h), scatter_checks (kernel_scatter.h).
 
 They decide on the quantities the sweeps hold at every value: a frame's 16-byte
 chunk count from its aligned-down start, its partial first and last chunk, and
@@ -37,8 +37,8 @@ def constants():
     code_match(h, r"for \(uint64_t k0 = lane; k0 < chunks; k0 \+= 64ull \* kUnroll\)")
     code_match(h, r"const uint64_t k = k0 \+ 64ull \* u;")
     code_match(h, r"if \(k >= f_hi\) \{")
-    ptile = code_constant("multi.hip", r"const uint64_t f = t \* (\d+) \+ lane;")
-    stride = code_constant("multi.hip", r"for \(uint32_t k = lane; k < total; k \+= (\d+)\) \{")
+    ptile = code_constant("kernel_pack.h", r"const uint64_t f = t \* (\d+) \+ lane;")
+    stride = code_constant("kernel_pack.h", r"for \(uint32_t k = lane; k < total; k \+= (\d+)\) \{")
     assert tile == ptile == stride == 64
     return 64, 64 * unroll
 

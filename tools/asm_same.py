@@ -8,10 +8,12 @@ assembly (`make asm` -> build/asm/checksummer-gfx950.s), ignoring labels,
 comments and directives.  Use it to tell whether profiles recorded at REV still
 describe the product's kernels:
 
-    python3 tools/asm_same.py <rev> [multi.hip | host_path.hip] [--diff]
+    python3 tools/asm_same.py <rev> [<source>.hip] [--diff]
 
-With a second source file named, its kernels are compared instead (both sides
-compiled into the scratch directory).
+With a second source file named -- any .hip under xsknf_amd/csrc: multi.hip
+(its kernels are kernel_pack.h's), forward_device.hip, plan_device.hip,
+route_device.hip, host_path.hip -- its kernels are compared instead (both
+sides compiled into the scratch directory).
 
 --diff prints the instruction diff of every kernel that is not identical
 (a renamed twin is matched by name with its template arguments removed).
@@ -33,7 +35,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-inline-asm", "-fvisibility=hidden", "--offload-arch=gfx950",
          "--cuda-device-only", "-S"]
 CSRC = "xsknf_amd/csrc"
-SOURCES = ["checksummer.hip", "multi.hip", "host_path.hip"]
+PRODUCT = "checksummer.hip"
 
 
 def files_at(rev, source):
@@ -50,7 +52,7 @@ def compile_asm(cwd, source, out):
 def kernels(path):
     out, cur = {}, None
     for line in open(path):
-        m = re.match(r"^(_ZN(?:9xsknf_gpu|12_GLOBAL__N_1)\w+):", line)   # (multi.hip: an unnamed namespace)
+        m = re.match(r"^(_ZN(?:9xsknf_gpu|12_GLOBAL__N_1)\w+):", line)   # (unnamed: multi.hip's kernels before kernel_pack.h)
         if m:
             cur = m.group(1)
             out[cur] = []
@@ -91,12 +93,12 @@ def main():
         return vs_ab()
     args = [a for a in sys.argv[1:] if a != "--diff"]
     show = "--diff" in sys.argv[1:]
-    if len(args) not in (1, 2) or (len(args) == 2 and os.path.basename(args[1]) not in SOURCES):
+    source = os.path.basename(args[1]) if len(args) == 2 else PRODUCT
+    if len(args) not in (1, 2) or not (source.endswith(".hip") and os.path.isfile(os.path.join(ROOT, CSRC, source))):
         raise SystemExit(__doc__)
     rev = args[0]
-    source = os.path.basename(args[1]) if len(args) == 2 else SOURCES[0]
     with tempfile.TemporaryDirectory() as d:
-        if source == SOURCES[0]:
+        if source == PRODUCT:
             cur = os.path.join(ROOT, "build", "asm", "checksummer-gfx950.s")
             subprocess.run(["make", "-C", ROOT, "asm"], check=True, stdout=subprocess.DEVNULL)
         else:

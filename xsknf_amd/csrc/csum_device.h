@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "checksummer_internal.h"
+#include "desc_rules.h"
 
 namespace xsknf_gpu {
 
@@ -20,10 +21,6 @@ constexpr int kSlotBytes = 128;  // register kernel: per-group LDS header window
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) uint8_t lds_u8;
-
-__device__ __forceinline__ uint64_t umem_offset(uint64_t addr) {
-  return (addr & XSKNF_GPU_UNALIGNED_BUF_ADDR_MASK) + (addr >> XSKNF_GPU_UNALIGNED_BUF_OFFSET_SHIFT);
-}
 
 __device__ __forceinline__ void compiler_barrier() {
   __builtin_amdgcn_wave_barrier();
@@ -219,9 +216,9 @@ struct FrameRef {
 
 __device__ __forceinline__ FrameRef make_ref(const KernelArgs &a, uint64_t addr, uint32_t len, bool exists) {
   FrameRef r;
-  const uint64_t off = umem_offset(addr);
+  const uint64_t off = desc_offset(addr);
   // (frames of 2 GiB and more are treated as out of range: lengths are ints here)
-  const bool in_range = off <= a.umem_size && len <= a.umem_size - off && len < 0x80000000u;
+  const bool in_range = in_umem(off, len, a.umem_size) && len < 0x80000000u;
   r.exists = exists;
   r.live = exists && in_range && len >= 14;
   r.len = static_cast<int>(len);

@@ -1,34 +1,17 @@
 // forward_args.h -- what the two forms of the frame forward (forward_host.cpp,
 // forward_device.hip; include/xsknf_gpu.h xsknf_gpu_forward_*) share: the
-// address translation, the range rule and the argument checks.  Plain C++, no
-// GPU call, so that forward_host.cpp builds without HIP.
+// argument checks.  Plain C++, no GPU call, so that forward_host.cpp builds
+// without HIP.
 #pragma once
 #include <errno.h>
 #include <stdint.h>
 
 #include "../../include/xsknf_gpu.h"
 
-#if defined(__HIPCC__)
-#define XSKNF_FWD_HD __host__ __device__
-#else
-#define XSKNF_FWD_HD
-#endif
-
 namespace xsknf_gpu {
 namespace forward {
 
 constexpr uint32_t kMaxInterfaces = XSKNF_GPU_ROUTE_MAX_INTERFACES;
-
-// xsknf_rt.c addr_offset (xsk_umem__add_offset_to_addr, src/xsknf.c:509):
-// identity in aligned mode.
-XSKNF_FWD_HD inline uint64_t addr_offset(uint64_t addr) {
-  return (addr & XSKNF_GPU_UNALIGNED_BUF_ADDR_MASK) + (addr >> XSKNF_GPU_UNALIGNED_BUF_OFFSET_SHIFT);
-}
-
-// [off, off + len) lies inside a UMEM of `size` bytes
-XSKNF_FWD_HD inline bool in_range(uint64_t off, uint32_t len, uint64_t size) {
-  return off <= size && len <= size - off;
-}
 
 inline bool overlap(uintptr_t a, uint64_t na, uintptr_t b, uint64_t nb) {
   return na && nb && a < b + nb && b < a + na;

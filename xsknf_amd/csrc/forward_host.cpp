@@ -12,6 +12,7 @@
 #include <string.h>
 
 #include "../../include/xsknf_gpu.h"
+#include "desc_rules.h"
 #include "forward_args.h"
 
 extern "C" {
@@ -35,9 +36,9 @@ int xsknf_gpu_forward_host(const uint8_t *rx_umem, uint64_t rx_umem_size, uint8_
     uint8_t *dst = tx_umems[i];
     if (dst && dst != rx_umem) {   // (else the rx UMEM is this interface's own: :572-579)
       for (uint64_t j = base; j < base + c; ++j) {
-        const uint64_t off = addr_offset(tx_descs[j].addr);
+        const uint64_t off = xsknf_gpu::desc_offset(tx_descs[j].addr);
         const uint32_t len = tx_descs[j].len;
-        if (!in_range(off, len, rx_umem_size) || !in_range(off, len, tx_umem_sizes[i])) {
+        if (!xsknf_gpu::in_umem(off, len, rx_umem_size) || !xsknf_gpu::in_umem(off, len, tx_umem_sizes[i])) {
           ++st[2];
           continue;
         }

@@ -74,6 +74,7 @@
 
 #include "../../include/xsknf_gpu.h"
 #include "checksummer_internal.h"
+#include "desc_rules.h"
 
 namespace {
 
@@ -153,10 +154,6 @@ int fail(hipError_t e, const char *where) {
   if (e == hipErrorNoDevice) return xsknf_gpu::set_device_error(e, 0, where);
   xsknf_gpu::set_error(e, where);
   return -EIO;
-}
-
-uint64_t umem_offset(uint64_t addr) {
-  return (addr & XSKNF_GPU_UNALIGNED_BUF_ADDR_MASK) + (addr >> XSKNF_GPU_UNALIGNED_BUF_OFFSET_SHIFT);
 }
 
 // ---- RESIDENT: the device's one resident kernel (ResService) --------------------
@@ -551,10 +548,10 @@ int stage_frames(xsknf_gpu_ctx *c, Slot &s, uint32_t n, xsknf_gpu::KernelArgs &a
   bool sorted = true;
   uint64_t prev = 0;
   for (uint32_t i = 0; i < n; ++i) {
-    const uint64_t off = umem_offset(s.descs[i].addr);
+    const uint64_t off = xsknf_gpu::desc_offset(s.descs[i].addr);
     const uint32_t len = s.descs[i].len;
     s.offs[i] = off;
-    if (off > c->umem_size || len > c->umem_size - off || len == 0) continue;
+    if (!xsknf_gpu::in_umem(off, len, c->umem_size) || len == 0) continue;
     if (off < prev) sorted = false;
     prev = off;
     s.order.push_back(i);

@@ -6,7 +6,7 @@
 //
 // One launch of a persistent grid; no block waits on another.  Every block
 // reads the <= 33 counts the router left and builds the interface bases in LDS.
-// The work is dealt as multi.hip pack_frames deals it: a wave takes 64
+// The work is dealt as kernel_pack.h pack_frames deals it: a wave takes 64
 // consecutive entries (a tile), prefix-sums their 16-byte chunk counts and its
 // lanes take the tile's chunks round robin, kUnroll rounds at a time, so a
 // 9000-byte frame and the 1-byte frames beside it keep all 64 lanes busy.
@@ -23,6 +23,7 @@
 #include <stdint.h>
 
 #include "../../include/xsknf_gpu.h"
+#include "desc_rules.h"
 #include "forward_args.h"
 
 // Destination stores non-temporal (the product: DESIGN 4.2's A/B) or plain (0)
@@ -133,11 +134,12 @@ __global__ void __launch_bounds__(kThreads) forward_frames(const uint8_t *rx, ui
       dst = s_dst[lo];
       if (dst) {
         const xsknf_gpu_desc d = tx_descs[e];
-        off = addr_offset(d.addr);
+        off = desc_offset(d.addr);
         len = d.len;
-        if (in_range(off, len, rx_size) && in_range(off, len, s_dsize[lo])) {
+        if (in_umem(off, len, rx_size) && in_umem(off, len, s_dsize[lo])) {
           c_frames += 1;
           c_bytes += len;
+          // desc_rules.h chunk_count(off, len), written out: the call reorders the kernel and measured slower
           if (len) nch = ((off & 15) + len + 15) >> 4;
         } else {
           c_skipped += 1;

@@ -21,6 +21,7 @@
 
 #include "../../include/xsknf_gpu.h"
 #include "block_scan.h"
+#include "desc_rules.h"
 
 namespace xsknf_gpu {
 namespace plan {
@@ -29,7 +30,6 @@ constexpr int kThreads = 256;
 constexpr int kPerThread = 8;
 constexpr uint32_t kTile = kThreads * kPerThread;   // frames per block
 constexpr uint32_t kMaxShards = 64;
-constexpr uint64_t kOutOfRange = 1ull << 47;        // as shard_plan.cpp
 constexpr unsigned long long kNone = ~0ull;
 
 // The workspace, in u64 words.  The first kResultWords are what the host reads
@@ -62,19 +62,11 @@ __device__ inline void store_desc(uint4 *out, uint64_t f, uint64_t addr, uint32_
   out[f] = make_uint4(static_cast<uint32_t>(addr), static_cast<uint32_t>(addr >> 32), len, options);
 }
 
-__device__ inline uint64_t desc_offset(uint64_t addr) {
-  return (addr & XSKNF_GPU_UNALIGNED_BUF_ADDR_MASK) + (addr >> XSKNF_GPU_UNALIGNED_BUF_OFFSET_SHIFT);
-}
-
-__device__ inline bool in_umem(uint64_t off, uint32_t len, uint64_t umem_size) {
-  return off <= umem_size && len <= umem_size - off;
-}
-
 // Bytes of a frame's slot in its shard's packed buffer (shard_plan.cpp
 // xsknf_gpu_shard_pack_plan): whole 16-byte chunks at the frame's address mod 16.
 __device__ inline uint64_t slot_len(uint64_t umem_addr, uint64_t off, uint32_t len, uint64_t umem_size) {
   if (len == 0 || !in_umem(off, len, umem_size)) return 0;
-  return (((umem_addr + off) & 15) + len + 15) & ~15ull;
+  return slot_bytes(umem_addr + off, len);
 }
 
 // The u64 block scan (block_scan.h), shared with the router's kernels.

@@ -25,7 +25,7 @@ namespace xsknf_gpu {
 // Rewrite one parked check: lane `piece` (0..3) of the record's 4 lanes.
 __device__ __forceinline__ void rewrite_check(const KernelArgs &args, uint32_t f, uint32_t r,
                                               const xsknf_gpu_desc &d, int piece) {
-  uint8_t *fp = args.umem + umem_offset(d.addr);
+  uint8_t *fp = args.umem + desc_offset(d.addr);
   uint8_t *chk = fp + record_check_offset(r);
   const uint16_t c = record_check(r);
   uint8_t *sec = chk - (reinterpret_cast<uintptr_t>(chk) & 63);   // keeps global addressing
@@ -75,7 +75,7 @@ __device__ __forceinline__ void scatter_dense(const KernelArgs &args) {
     for (int k = 0; k < kScatterU; ++k) {
       const uint32_t t = t0 + k * nthreads;
       rec[k] = t < total && is_record(r[k]);
-      uint8_t *fp = args.umem + umem_offset(d[k].addr);
+      uint8_t *fp = args.umem + desc_offset(d[k].addr);
       uint8_t *chk = fp + record_check_offset(r[k]);
       uint8_t *sec = chk - (reinterpret_cast<uintptr_t>(chk) & 63);   // keeps global addressing
       whole[k] = rec[k] && sec >= fp && sec + 64 <= fp + d[k].len && (reinterpret_cast<uintptr_t>(chk) & 63) != 63;

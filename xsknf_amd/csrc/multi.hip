@@ -38,25 +38,25 @@
 //   * xsknf_gpu_multi_scatter_dev -- either scatter for descriptors that lie on
 //     the root device: planned there (plan_device.hip) instead of on the host,
 //     then the same placement and moves (place_shards / send_shards below).
+// Host code only: the kernels (shard_counters, pack_frames, apply_records) are kernel_pack.h's.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 #include <errno.h>
 #include <stdint.h>
 #include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 #include <time.h>
 #include <new>
 #include <vector>
 
 #include "../../include/xsknf_gpu.h"
 #include "checksummer_internal.h"
+#include "kernel_pack.h"
 #include "plan_device.h"
 
 namespace {
 
-constexpr uint64_t kOutOfRange = 1ull << 47;   // an address past any UMEM: verdict -1, no bytes
-constexpr uint32_t kFingerprintMod = 65521;
+using namespace xsknf_gpu::multi;
+
 // Bytes per ncclSend / ncclRecv of a scatter.  One ncclSend of a whole span
 // past 1 GiB delivered only part of it with this image's RCCL (a send to self
 // of the 2 GiB and 16 GiB spans of 1M and 8M IMIX frames: the bytes from 1 GiB
@@ -65,10 +65,6 @@ constexpr uint32_t kFingerprintMod = 65521;
 // (profiles/r06/multi_p2p_pieces.jsonl; the probe, with the piece size as an
 // environment knob, is in commit cca61bb's tools/diag_multi_p2p.py).
 constexpr uint64_t kP2PPiece = 1ull << 28;
-
-__host__ __device__ inline uint64_t umem_offset(uint64_t addr) {
-  return (addr & XSKNF_GPU_UNALIGNED_BUF_ADDR_MASK) + (addr >> XSKNF_GPU_UNALIGNED_BUF_OFFSET_SHIFT);
-}
 
 int nccl_fail(ncclResult_t r, const char *where) {
   char buf[256];
@@ -88,125 +84,10 @@ double now_s() {
   return ts.tv_sec + ts.tv_nsec * 1e-9;
 }
 
-// Per frame of one shard: [frames, bytes, drops, forwards, checks, weighted
-// checks] -- the bytes over every descriptor's len (xsknf_amd/shard.py
-// counters()), the checks over the frames of at least 42 bytes inside the span
-// (the UDP check of an ihl-5 frame at +40, as bench.py check_fingerprint reads
-// it), weighted by (global offset mod 65521) + 1 so that a check landing in
-// another frame shows.  One wave per 64 frames, a block sum, one atomic per
-// counter and block (vector atomics to device memory).
-__global__ void __launch_bounds__(256) shard_counters(const uint8_t *umem, uint64_t span,
-                                                      const xsknf_gpu_desc *descs, const int32_t *verdicts,
-                                                      uint64_t n, uint64_t base, unsigned long long *out) {
-  unsigned long long c[XSKNF_GPU_MULTI_COUNTERS] = {};
-  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += gridDim.x * 256ull) {
-    const xsknf_gpu_desc d = descs[i];
-    const int32_t v = verdicts[i];
-    c[0] += 1;
-    c[1] += d.len;
-    c[2] += v == -1;
-    c[3] += v >= 0;
-    const uint64_t off = umem_offset(d.addr);
-    if (d.len >= 42 && off <= span && d.len <= span - off) {
-      const unsigned long long ck = umem[off + 40] | static_cast<unsigned>(umem[off + 41]) << 8;
-      c[4] += ck;
-      c[5] += ck * ((off + base) % kFingerprintMod + 1);
-    }
-  }
-  __shared__ unsigned long long red[XSKNF_GPU_MULTI_COUNTERS][4];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < XSKNF_GPU_MULTI_COUNTERS; ++k) {
-    unsigned long long x = c[k];
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-    if (lane == 0) red[k][wv] = x;
-  }
-  __syncthreads();
-  if (threadIdx.x < XSKNF_GPU_MULTI_COUNTERS) {
-    const int k = threadIdx.x;
-    atomicAdd(&out[k], red[k][0] + red[k][1] + red[k][2] + red[k][3]);
-  }
-}
-
-// Root: copy frames [0, n) of one shard into its packed buffer.  Frame f's
-// bytes lie in the 16-byte aligned chunks [src & ~15, round16(src + len)) of
-// memory (src = its address) and go to the slot at dst & ~15 of the packed
-// buffer, whose length is exactly those chunks (dst = src mod 16 + the slot's
-// start): whole chunks move, and the bytes around the frame in its first and
-// last chunk are copied with it into its own slot.  One wave per 64 frames:
-// the tile's chunk counts are prefix-summed across the wave and the lanes deal
-// the tile's chunks round robin (a 64-B frame is 4-5 chunks, a jumbo one 563).
-// A chunk reaching past the UMEM's end is copied byte by byte.
-__global__ void __launch_bounds__(256) pack_frames(const uint8_t *umem, uint64_t umem_size,
-                                                   const xsknf_gpu_desc *orig, const xsknf_gpu_desc *packed,
-                                                   uint64_t n, uint8_t *dst) {
-  __shared__ uint32_t pre[4][65];
-  __shared__ uint64_t src_of[4][64], dst_of[4][64];   // a frame's first chunk and its slot (read by any lane)
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const uint64_t tiles = (n + 63) / 64;
-  for (uint64_t t = blockIdx.x * 4ull + wv; t < tiles; t += gridDim.x * 4ull) {
-    const uint64_t f = t * 64 + lane;
-    uint64_t s0 = 0, d0 = 0;   // the first chunk's address (absolute) and its slot offset in dst
-    uint32_t nch = 0;
-    if (f < n) {
-      const xsknf_gpu_desc o = orig[f], q = packed[f];
-      const uint64_t src = reinterpret_cast<uintptr_t>(umem) + umem_offset(o.addr);
-      if (q.addr != kOutOfRange && o.len > 0) {
-        s0 = src & ~15ull;
-        d0 = q.addr & ~15ull;
-        nch = static_cast<uint32_t>(((src & 15) + o.len + 15) >> 4);
-      }
-    }
-    // inclusive scan of the chunk counts over the wave
-    uint32_t x = nch;
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t y = __shfl_up(x, o);
-      if (lane >= o) x += y;
-    }
-    pre[wv][lane + 1] = x;
-    if (lane == 0) pre[wv][0] = 0;
-    src_of[wv][lane] = s0;
-    dst_of[wv][lane] = d0;
-    __builtin_amdgcn_wave_barrier();   // (one wave's LDS accesses complete in order)
-    const uint32_t total = __shfl(x, 63);
-    const uint64_t begin = reinterpret_cast<uintptr_t>(umem), end = begin + umem_size;
-    for (uint32_t k = lane; k < total; k += 64) {
-      // the frame j of the tile whose chunks hold chunk k: pre[j] <= k < pre[j + 1]
-      int lo = 0, hi = 63;
-      while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (pre[wv][mid] <= k) lo = mid; else hi = mid - 1;
-      }
-      const uint32_t c = k - pre[wv][lo];
-      // (from LDS, not by a lane shuffle: the loop's last round leaves lanes
-      // inactive, and a shuffle reads nothing from an inactive lane)
-      const uint64_t sa = src_of[wv][lo] + 16ull * c, da = dst_of[wv][lo] + 16ull * c;
-      if (sa >= begin && sa + 16 <= end) {
-        *reinterpret_cast<uint4 *>(dst + da) = *reinterpret_cast<const uint4 *>(sa);
-      } else {   // a chunk reaching before the UMEM's first byte or past its last
-        for (uint64_t b = sa > begin ? sa : begin; b < sa + 16 && b < end; ++b)
-          dst[da + (b - sa)] = *reinterpret_cast<const uint8_t *>(b);
-      }
-    }
-    __builtin_amdgcn_wave_barrier();   // pre[wv] is rewritten by the next tile
-  }
-}
-
-// Root: the returned records / verdicts of the whole batch, in place: a record
-// (make_record(u, check), checksummer_internal.h) writes the check's two bytes, low
-// byte first, at the frame's offset u + 6 (checksummer_user.c:108) and becomes
-// the forward verdict (:110-111); any other value is already the verdict.
-__global__ void __launch_bounds__(256) apply_records(uint8_t *umem, const xsknf_gpu_desc *orig, int32_t *verdicts,
-                                                     uint64_t n, int32_t fwd) {
-  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += gridDim.x * 256ull) {
-    const uint32_t r = static_cast<uint32_t>(verdicts[i]);
-    if (!xsknf_gpu::is_record(r)) continue;
-    uint8_t *p = umem + umem_offset(orig[i].addr) + xsknf_gpu::record_check_offset(r);
-    const uint16_t c = xsknf_gpu::record_check(r);
-    p[0] = static_cast<uint8_t>(c);
-    p[1] = static_cast<uint8_t>(c >> 8);
-    verdicts[i] = fwd;
-  }
+// Blocks of 256 threads for n items, one each, at most `cap` (the kernels stride).
+unsigned grid_for(uint64_t n, uint64_t cap) {
+  const uint64_t want = (n + 255) / 256;
+  return static_cast<unsigned>(want < cap ? want : cap);
 }
 
 struct Shard {
@@ -369,8 +250,9 @@ int grouped_moves(xsknf_gpu_multi *m, const std::vector<Move> &moves, const char
 // planner: the cuts, each shard's span (2 per shard) or packed bytes (1 per
 // shard), each shard's frame bytes.
 struct Plan {
-  bool packed = false;
+  bool packed;
   std::vector<uint64_t> bounds, ext, bytes;
+  Plan(int N, bool pk) : packed(pk), bounds(N + 1), ext(pk ? N : 2 * N), bytes(N) {}
 };
 
 // The planned shards' fields and device buffers (packed: the root's staging
@@ -419,9 +301,7 @@ int send_shards(xsknf_gpu_multi *m, int root, const uint8_t *umem, uint64_t umem
     for (int k = 0; k < N && e == hipSuccess; ++k) {
       const uint64_t frames = p.bounds[k + 1] - p.bounds[k];
       if (!frames) continue;
-      const uint64_t want = (frames + 255) / 256;
-      const unsigned grid = static_cast<unsigned>(want < 4096 ? want : 4096);
-      hipLaunchKernelGGL(pack_frames, dim3(grid), dim3(256), 0, rs.stream, umem, umem_size,
+      hipLaunchKernelGGL(pack_frames, dim3(grid_for(frames, 4096)), dim3(256), 0, rs.stream, umem, umem_size,
                          m->root_orig + p.bounds[k], m->root_descs + p.bounds[k], frames,
                          k == root ? rs.umem : m->root_pack + pk_lo[k]);
       e = hipGetLastError();
@@ -450,11 +330,40 @@ int send_shards(xsknf_gpu_multi *m, int root, const uint8_t *umem, uint64_t umem
   return 0;
 }
 
-// Each shard's sum of frame lengths, from host descriptors.
-void host_shard_bytes(const xsknf_gpu_desc *descs, Plan &p) {
-  p.bytes.assign(p.bounds.size() - 1, 0);
-  for (size_t k = 0; k + 1 < p.bounds.size(); ++k)
+// xsknf_gpu_multi_scatter and _scatter_packed: the plan on the host, the
+// descriptors every shard receives (rebased to its own span, or addressing its
+// packed bytes) staged on the root in global order, the placement, the moves.
+int scatter_host(xsknf_gpu_multi *m, int root, const uint8_t *umem, uint64_t umem_size, const xsknf_gpu_desc *descs,
+                 uint64_t n, bool packed, double *seconds) {
+  if (!m || root < 0 || root >= m->ndev || (n && (!umem || !descs))) return -EINVAL;
+  const int N = m->ndev;
+  Plan p(N, packed);
+  int rc = xsknf_gpu_shard_plan(descs, n, umem_size, static_cast<uint32_t>(N), p.bounds.data(),
+                                packed ? nullptr : p.ext.data());
+  if (rc) return rc;
+  std::vector<xsknf_gpu_desc> sent(n);
+  if (packed) {
+    rc = xsknf_gpu_shard_pack_plan(descs, n, reinterpret_cast<uintptr_t>(umem), umem_size, static_cast<uint32_t>(N),
+                                   p.bounds.data(), sent.data(), p.ext.data());
+    if (rc) return rc;
+  } else {
+    for (int k = 0; k < N; ++k)
+      xsknf_gpu_shard_rebase(descs + p.bounds[k], p.bounds[k + 1] - p.bounds[k], p.ext[2 * k], umem_size,
+                             sent.data() + p.bounds[k]);
+  }
+  hipError_t e = stage_root(m, root, descs, sent.data(), n);
+  if (e != hipSuccess)
+    return hip_fail(e, packed ? "multi packed scatter: root buffers" : "multi scatter: root descriptors");
+  for (int k = 0; k < N; ++k)   // each shard's sum of frame lengths
     for (uint64_t f = p.bounds[k]; f < p.bounds[k + 1]; ++f) p.bytes[k] += descs[f].len;
+  std::vector<uint64_t> pk_lo;
+  rc = place_shards(m, root, umem, p, pk_lo);
+  if (rc) return rc;
+  const double t0 = now_s();
+  rc = send_shards(m, root, umem, umem_size, n, p, pk_lo);
+  if (rc) return rc;
+  if (seconds) *seconds = now_s() - t0;
+  return 0;
 }
 
 }  // namespace
@@ -504,57 +413,12 @@ int xsknf_gpu_multi_create(struct xsknf_gpu_multi **out, const int *devices, int
 
 int xsknf_gpu_multi_scatter(struct xsknf_gpu_multi *m, int root, const uint8_t *umem, uint64_t umem_size,
                             const struct xsknf_gpu_desc *descs, uint64_t n, double *seconds) {
-  if (!m || root < 0 || root >= m->ndev || (n && (!umem || !descs))) return -EINVAL;
-  const int N = m->ndev;
-  Plan p;
-  p.bounds.resize(N + 1);
-  p.ext.resize(2 * N);
-  int rc = xsknf_gpu_shard_plan(descs, n, umem_size, static_cast<uint32_t>(N), p.bounds.data(), p.ext.data());
-  if (rc) return rc;
-  // the rebased descriptors of every shard (each relative to its own span),
-  // staged on the root device in global order
-  std::vector<xsknf_gpu_desc> rebased(n);
-  for (int k = 0; k < N; ++k)
-    xsknf_gpu_shard_rebase(descs + p.bounds[k], p.bounds[k + 1] - p.bounds[k], p.ext[2 * k], umem_size,
-                           rebased.data() + p.bounds[k]);
-  hipError_t e = stage_root(m, root, descs, rebased.data(), n);
-  if (e != hipSuccess) return hip_fail(e, "multi scatter: root descriptors");
-  host_shard_bytes(descs, p);
-  std::vector<uint64_t> pk_lo;
-  rc = place_shards(m, root, umem, p, pk_lo);
-  if (rc) return rc;
-  const double t0 = now_s();
-  rc = send_shards(m, root, umem, umem_size, n, p, pk_lo);
-  if (rc) return rc;
-  if (seconds) *seconds = now_s() - t0;
-  return 0;
+  return scatter_host(m, root, umem, umem_size, descs, n, false, seconds);
 }
 
 int xsknf_gpu_multi_scatter_packed(struct xsknf_gpu_multi *m, int root, const uint8_t *umem, uint64_t umem_size,
                                    const struct xsknf_gpu_desc *descs, uint64_t n, double *seconds) {
-  if (!m || root < 0 || root >= m->ndev || (n && (!umem || !descs))) return -EINVAL;
-  const int N = m->ndev;
-  Plan p;
-  p.packed = true;
-  p.bounds.resize(N + 1);
-  p.ext.resize(N);
-  int rc = xsknf_gpu_shard_plan(descs, n, umem_size, static_cast<uint32_t>(N), p.bounds.data(), nullptr);
-  if (rc) return rc;
-  std::vector<xsknf_gpu_desc> packed(n);
-  rc = xsknf_gpu_shard_pack_plan(descs, n, reinterpret_cast<uintptr_t>(umem), umem_size, static_cast<uint32_t>(N),
-                                 p.bounds.data(), packed.data(), p.ext.data());
-  if (rc) return rc;
-  hipError_t e = stage_root(m, root, descs, packed.data(), n);
-  if (e != hipSuccess) return hip_fail(e, "multi packed scatter: root buffers");
-  host_shard_bytes(descs, p);
-  std::vector<uint64_t> pk_lo;
-  rc = place_shards(m, root, umem, p, pk_lo);
-  if (rc) return rc;
-  const double t0 = now_s();
-  rc = send_shards(m, root, umem, umem_size, n, p, pk_lo);
-  if (rc) return rc;
-  if (seconds) *seconds = now_s() - t0;
-  return 0;
+  return scatter_host(m, root, umem, umem_size, descs, n, true, seconds);
 }
 
 int xsknf_gpu_multi_scatter_dev(struct xsknf_gpu_multi *m, int root, const uint8_t *umem, uint64_t umem_size,
@@ -565,11 +429,7 @@ int xsknf_gpu_multi_scatter_dev(struct xsknf_gpu_multi *m, int root, const uint8
   if (reinterpret_cast<uintptr_t>(descs_dev) & 15) return -EINVAL;   // the planner's 16-byte loads
   const int N = m->ndev;
   const double t0 = now_s();
-  Plan p;
-  p.packed = mode == XSKNF_GPU_PLAN_PACKED;
-  p.bounds.resize(N + 1);
-  p.ext.resize(p.packed ? N : 2 * N);
-  p.bytes.resize(N);
+  Plan p(N, mode == XSKNF_GPU_PLAN_PACKED);
   const char *what = "multi device-planned scatter: root buffers";
   hipError_t e = root_prepare(m, root, n);
   if (e == hipSuccess) e = root_buffer(m->root_plan, m->root_plan_cap, xsknf_gpu::plan_dev_workspace_bytes(n));
@@ -637,10 +497,8 @@ int xsknf_gpu_multi_counters(struct xsknf_gpu_multi *m, uint64_t *out) {
       e = hipMemsetAsync(s.counters, 0, sizeof(unsigned long long) * XSKNF_GPU_MULTI_COUNTERS, s.stream);
     const uint64_t frames = s.hi - s.lo;
     if (e == hipSuccess && frames) {
-      const uint64_t want = (frames + 255) / 256;
-      const unsigned grid = static_cast<unsigned>(want < 2048 ? want : 2048);
-      hipLaunchKernelGGL(shard_counters, dim3(grid), dim3(256), 0, s.stream, s.umem, s.b1 - s.b0, s.descs,
-                         s.verdicts, frames, s.b0, s.counters);
+      hipLaunchKernelGGL(shard_counters, dim3(grid_for(frames, 2048)), dim3(256), 0, s.stream, s.umem, s.b1 - s.b0,
+                         s.descs, s.verdicts, frames, s.b0, s.counters);
       e = hipGetLastError();
     }
     if (e != hipSuccess) return hip_fail(e, "multi counters: launch");
@@ -714,9 +572,8 @@ int xsknf_gpu_multi_return(struct xsknf_gpu_multi *m, uint32_t ingress_ifindex, 
   if (e == hipSuccess && m->n) {
     const int32_t fwd = opts->action == XSKNF_CSUM_ACTION_REDIRECT
                             ? static_cast<int32_t>((ingress_ifindex + 1u) % opts->num_interfaces) : -1;
-    const uint64_t want = (m->n + 255) / 256;
-    const unsigned grid = static_cast<unsigned>(want < 4096 ? want : 4096);
-    hipLaunchKernelGGL(apply_records, dim3(grid), dim3(256), 0, rs.stream, umem, m->root_orig, verdicts, m->n, fwd);
+    hipLaunchKernelGGL(apply_records, dim3(grid_for(m->n, 4096)), dim3(256), 0, rs.stream, umem, m->root_orig,
+                       verdicts, m->n, fwd);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(rs.stream);
   }

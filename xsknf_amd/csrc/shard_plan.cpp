@@ -8,21 +8,9 @@
 #include <stdint.h>
 
 #include "../../include/xsknf_gpu.h"
+#include "desc_rules.h"
 
-namespace {
-
-constexpr uint64_t kOutOfRange = 1ull << 47;   // an address past any UMEM: verdict -1, no bytes
-
-inline uint64_t umem_offset(uint64_t addr) {
-  return (addr & XSKNF_GPU_UNALIGNED_BUF_ADDR_MASK) + (addr >> XSKNF_GPU_UNALIGNED_BUF_OFFSET_SHIFT);
-}
-
-inline bool in_umem(const xsknf_gpu_desc &d, uint64_t umem_size) {
-  const uint64_t off = umem_offset(d.addr);
-  return off <= umem_size && d.len <= umem_size - off;
-}
-
-}  // namespace
+using namespace xsknf_gpu;
 
 extern "C" {
 
@@ -54,8 +42,8 @@ int xsknf_gpu_shard_plan(const struct xsknf_gpu_desc *descs, uint64_t n, uint64_
     for (uint32_t r = 0; r < nshards; ++r) {
       uint64_t b0 = UINT64_MAX, b1 = 0;
       for (uint64_t f = bounds[r]; f < bounds[r + 1]; ++f) {
-        if (!in_umem(descs[f], umem_size)) continue;
-        const uint64_t off = umem_offset(descs[f].addr);
+        const uint64_t off = desc_offset(descs[f].addr);
+        if (!in_umem(off, descs[f].len, umem_size)) continue;
         if (off < b0) b0 = off;
         if (off + descs[f].len > b1) b1 = off + descs[f].len;
       }
@@ -71,7 +59,8 @@ int xsknf_gpu_shard_rebase(const struct xsknf_gpu_desc *descs, uint64_t n, uint6
   if (n && (!descs || !out)) return -EINVAL;
   for (uint64_t i = 0; i < n; ++i) {
     const xsknf_gpu_desc d = descs[i];
-    out[i].addr = in_umem(d, umem_size) ? umem_offset(d.addr) - b0 : kOutOfRange;
+    const uint64_t off = desc_offset(d.addr);
+    out[i].addr = in_umem(off, d.len, umem_size) ? off - b0 : kOutOfRange;
     out[i].len = d.len;
     out[i].options = d.options;
   }
@@ -93,13 +82,13 @@ int xsknf_gpu_shard_pack_plan(const struct xsknf_gpu_desc *descs, uint64_t n, ui
       const xsknf_gpu_desc d = descs[f];
       packed[f].len = d.len;
       packed[f].options = d.options;
-      if (!in_umem(d, umem_size)) {
+      const uint64_t off = desc_offset(d.addr);
+      if (!in_umem(off, d.len, umem_size)) {
         packed[f].addr = kOutOfRange;
         continue;
       }
-      const uint64_t rs = (umem_addr + umem_offset(d.addr)) & 15;
-      packed[f].addr = pos + rs;
-      pos += d.len ? (rs + d.len + 15) & ~15ull : 0;
+      packed[f].addr = pos + ((umem_addr + off) & 15);
+      pos += d.len ? slot_bytes(umem_addr + off, d.len) : 0;
     }
     sizes[k] = pos;
   }
