@@ -617,6 +617,119 @@ XSKNF_GPU_API int xsknf_gpu_forward_host(const uint8_t *rx_umem, uint64_t rx_ume
 		uint8_t *const *tx_umems, const uint64_t *tx_umem_sizes, uint32_t num_interfaces,
 		const struct xsknf_gpu_desc *tx_descs, const uint64_t *counts, uint64_t *stats);
 
+/* ---- the firewall NF: a 5-tuple ACL lookup to one verdict per frame ----------
+ * The reference's second NF with the per-frame callback
+ * (examples/firewall/firewall_user.c:128-186): parse Ethernet / IPv4 / TCP or
+ * UDP, look the 13-byte 5-tuple up in an exact-match ACL, return the rule's
+ * action (-1: drop; otherwise a tx interface index; 0 where no rule matches).
+ * These calls do that for a whole batch, on the device or (the model the device
+ * is held to) on one CPU thread.  The verdicts are what xsknf_gpu_route_batch
+ * consumes; the UMEM is only read, and ingress_ifindex plays no part.
+ *
+ * Per frame, with f its bytes at umem + off,
+ *   off = (addr & XSKNF_GPU_UNALIGNED_BUF_ADDR_MASK) + (addr >> 48),
+ * and len its length:
+ *   0. not (off <= umem_size && len <= umem_size - off)   -> -1, no byte read
+ *   1. len < 14                                           -> -1
+ *   2. f[12..13] != 08 00                                 ->  0
+ *   3. len < 34                                           -> -1
+ *   4. next = 14 + 4 * (f[14] & 15)       (the ihl nibble is not validated: 0..15;
+ *                                          below 5 the ports overlap the IP header)
+ *   5. f[23] == 6 (TCP):  next + 20 > len                 -> -1
+ *      f[23] == 17 (UDP): next + 8 > len                  -> -1
+ *      any other protocol                                 ->  0
+ *   6. key = { saddr f[26..29], daddr f[30..33], sport f[next..next+1],
+ *              dport f[next+2..next+3], proto f[23] }, all as they lie in the
+ *      frame (network order), as the reference's struct session_id holds them
+ *   7. the action of the rule whose key equals this key, or 0 if there is none.
+ *
+ * The ACL is an exact-match map, the last rule winning among equal keys
+ * (khashmap_update_elem replaces the value).  Nothing else of the reference's
+ * khashmap is kept: the table is open addressing with linear probing over a
+ * power-of-two number of 16-byte key slots {saddr, daddr, sport | dport << 16,
+ * proto}, proto 0 marking an empty slot, and the actions in a parallel int32
+ * array that is read only on a hit (20 bytes per slot in all); the hash is a
+ * multiply / xor-shift mix of the key's four words (xsknf_amd/csrc/acl_table.h).
+ * At least one slot is always empty, so every probe sequence ends. */
+#define XSKNF_GPU_ACL_MAX_RULES 1000000u   /* MAX_ACL_SIZE, examples/firewall/firewall.h */
+#define XSKNF_GPU_ACL_MAX_SLOTS (1u << 24)
+
+struct xsknf_gpu_acl_rule {
+	uint32_t saddr, daddr;   /* network order (as in_addr.s_addr) */
+	uint16_t sport, dport;   /* network order */
+	uint8_t proto;           /* 6 or 17; a rule with any other can never match */
+	uint8_t pad[3];          /* ignored */
+	int32_t action;          /* any int32: -1 drops, the rest is the caller's (atoi's result) */
+};
+
+struct xsknf_gpu_acl;        /* opaque */
+
+struct xsknf_gpu_acl_info {
+	uint32_t rules;          /* distinct keys in the table */
+	uint32_t slots;          /* key slots (a power of two > rules) */
+	uint32_t max_probe;      /* slots looked at for the worst-placed rule (0 for an empty ACL) */
+	uint32_t reserved;
+	uint64_t device_bytes;   /* 20 * slots (0: built where no device was visible) */
+};
+
+/* Read the reference's ACL text (init_acl, firewall_user.c:53-116): the rule
+ * count, then records `saddr daddr sport dport PROTO ACTION` separated by any
+ * white space; dotted-quad addresses (inet_aton), decimal ports of which the
+ * low 16 bits count (htons), PROTO TCP or UDP, ACTION DROP (-1) or atoi's
+ * reading of it (0 for a word that is no number).  At most `cap` rules are
+ * written to rules_out (may be NULL with cap 0) and *n_out is the file's count;
+ * the whole file is validated either way.  No GPU call.
+ * Where the reference exits, we return: -errno when the file cannot be opened
+ * (-ENOENT ...), -EINVAL for an unknown protocol or a count that differs from the
+ * records.  Where the reference goes on silently we return -EINVAL as well: an
+ * address inet_aton rejects (the reference keeps the previous record's address);
+ * an address longer than 15, a protocol longer than 3 or an action longer than
+ * 4 characters (the reference overruns its buffers); a count or a port that is
+ * not a decimal number below 2^32, or a last record cut short (the reference's
+ * fscanf loop then reads garbage or never ends); more than
+ * XSKNF_GPU_ACL_MAX_RULES rules (the reference overruns its element pool).
+ * -ENOSPC when cap is less than the count (*n_out is set: ask again). */
+XSKNF_GPU_API int xsknf_gpu_acl_parse(const char *path, struct xsknf_gpu_acl_rule *rules_out, uint32_t cap,
+		uint32_t *n_out);
+/* Build the table from n rules on the calling thread (deterministic: the same
+ * rules give the same table) and upload it to the current device, where it
+ * stays until _destroy; a host copy is kept for xsknf_gpu_firewall_host.
+ * slots == 0: the smallest power of two >= 2 n, at least 64.  Otherwise slots
+ * must be a power of two, at most XSKNF_GPU_ACL_MAX_SLOTS and greater than the
+ * number of distinct keys.  Rules with a protocol other than 6 and 17 are left
+ * out; n == 0 gives a valid ACL that matches nothing.  In a process that sees
+ * no HIP device the ACL is built on the host alone (device_bytes 0): it serves
+ * xsknf_gpu_firewall_host, and xsknf_gpu_firewall_batch returns -ENODEV for it
+ * -- there is no CPU path behind the device call.  -EINVAL for a NULL
+ * acl_out, a NULL rules with n > 0 or a bad slots; -ENOMEM; -EIO on a HIP error
+ * (xsknf_gpu_last_error()). */
+XSKNF_GPU_API int xsknf_gpu_acl_create(struct xsknf_gpu_acl **acl_out, const struct xsknf_gpu_acl_rule *rules,
+		uint32_t n, uint32_t slots);
+XSKNF_GPU_API int xsknf_gpu_acl_info(const struct xsknf_gpu_acl *acl, struct xsknf_gpu_acl_info *info);
+/* Free the table on the device and the host (no batch that uses it may be in
+ * flight).  -EINVAL for NULL. */
+XSKNF_GPU_API int xsknf_gpu_acl_destroy(struct xsknf_gpu_acl *acl);
+
+/* verdicts[i] = the firewall's verdict for descs[i], i < n, on the current
+ * device (the one the ACL was created on), asynchronously on `stream` (a
+ * hipStream_t; NULL: the default stream).  umem (16-byte aligned), descs
+ * (16-byte aligned) and verdicts (4-byte aligned) are device memory.  The frame
+ * bytes are read as aligned 4-byte words that each hold at least one byte of
+ * rule 0's [off, off + len), so up to 3 bytes around a frame at the UMEM's edge
+ * are read with it: they lie inside any device allocation.  Nothing but
+ * verdicts[0 .. n) is written.  n == 0 succeeds without a launch.  -EINVAL,
+ * before any GPU call: a NULL acl, a misaligned umem, descs or verdicts, and
+ * with n > 0 a NULL umem, descs or verdicts.  -EIO on a HIP error, with
+ * xsknf_gpu_last_error() set. */
+XSKNF_GPU_API int xsknf_gpu_firewall_batch(const uint8_t *umem, uint64_t umem_size,
+		const struct xsknf_gpu_desc *descs, uint32_t n, const struct xsknf_gpu_acl *acl, int32_t *verdicts,
+		void *stream);
+/* The same on host arrays over the ACL's host copy: one thread, byte reads
+ * only, no GPU call and no alignment asked.  -EINVAL for a NULL acl and, with
+ * n > 0, a NULL umem, descs or verdicts. */
+XSKNF_GPU_API int xsknf_gpu_firewall_host(const uint8_t *umem, uint64_t umem_size,
+		const struct xsknf_gpu_desc *descs, uint32_t n, const struct xsknf_gpu_acl *acl, int32_t *verdicts);
+
 /* Text of the last HIP error seen by this library, on any thread (a copy
  * private to the calling thread). */
 XSKNF_GPU_API const char *xsknf_gpu_last_error(void);

@@ -57,7 +57,16 @@ EXPORTED_SYMBOLS = (
     "xsknf_gpu_route_host",
     "xsknf_gpu_forward_frames",
     "xsknf_gpu_forward_host",
+    "xsknf_gpu_acl_parse",
+    "xsknf_gpu_acl_create",
+    "xsknf_gpu_acl_info",
+    "xsknf_gpu_acl_destroy",
+    "xsknf_gpu_firewall_batch",
+    "xsknf_gpu_firewall_host",
 )
+
+ACL_MAX_RULES = 1000000     # XSKNF_GPU_ACL_MAX_RULES
+ACL_MAX_SLOTS = 1 << 24     # XSKNF_GPU_ACL_MAX_SLOTS
 
 ROUTE_MAX_INTERFACES = 32   # XSKNF_GPU_ROUTE_MAX_INTERFACES
 FORWARD_STATS = 3           # XSKNF_GPU_FORWARD_STATS
@@ -119,6 +128,13 @@ class ShardInfo(ctypes.Structure):
                 ("span_lo", ctypes.c_uint64), ("span_hi", ctypes.c_uint64),
                 ("frame_bytes", ctypes.c_uint64),
                 ("umem", ctypes.c_void_p), ("descs", ctypes.c_void_p), ("verdicts", ctypes.c_void_p)]
+
+
+class AclInfo(ctypes.Structure):
+    """struct xsknf_gpu_acl_info (include/xsknf_gpu.h)."""
+
+    _fields_ = [("rules", ctypes.c_uint32), ("slots", ctypes.c_uint32), ("max_probe", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32), ("device_bytes", ctypes.c_uint64)]
 
 
 class XsknfGpuError(RuntimeError):
@@ -267,6 +283,18 @@ def load() -> ctypes.CDLL:
     lib.xsknf_gpu_forward_frames.argtypes = [vp, u64, vp, vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp, vp, vp]
     lib.xsknf_gpu_forward_host.restype = ctypes.c_int
     lib.xsknf_gpu_forward_host.argtypes = [vp, u64, vp, vp, ctypes.c_uint32, vp, vp, vp]
+    lib.xsknf_gpu_acl_parse.restype = ctypes.c_int
+    lib.xsknf_gpu_acl_parse.argtypes = [ctypes.c_char_p, vp, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
+    lib.xsknf_gpu_acl_create.restype = ctypes.c_int
+    lib.xsknf_gpu_acl_create.argtypes = [ctypes.POINTER(vp), vp, ctypes.c_uint32, ctypes.c_uint32]
+    lib.xsknf_gpu_acl_info.restype = ctypes.c_int
+    lib.xsknf_gpu_acl_info.argtypes = [vp, ctypes.POINTER(AclInfo)]
+    lib.xsknf_gpu_acl_destroy.restype = ctypes.c_int
+    lib.xsknf_gpu_acl_destroy.argtypes = [vp]
+    lib.xsknf_gpu_firewall_batch.restype = ctypes.c_int
+    lib.xsknf_gpu_firewall_batch.argtypes = [vp, u64, vp, ctypes.c_uint32, vp, vp, vp]
+    lib.xsknf_gpu_firewall_host.restype = ctypes.c_int
+    lib.xsknf_gpu_firewall_host.argtypes = [vp, u64, vp, ctypes.c_uint32, vp, vp]
     lib.xsknf_gpu_pool_guard_trips.restype = ctypes.c_int
     lib.xsknf_gpu_pool_guard_trips.argtypes = [ctypes.POINTER(ctypes.c_uint32), ctypes.c_int]
     _lib = lib

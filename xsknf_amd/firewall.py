@@ -1,0 +1,164 @@
+"""The firewall NF: a 5-tuple ACL lookup to one verdict per frame.
+
+The reference's second NF with the per-frame callback
+(examples/firewall/firewall_user.c:128-186): parse Ethernet / IPv4 / TCP or UDP,
+look the 13-byte 5-tuple up in an exact-match ACL and return the rule's action
+(-1 drops, anything else names a tx interface, 0 where no rule matches).  The
+rules per frame are in include/xsknf_gpu.h ("the firewall NF").
+
+`Acl` holds the table (xsknf_gpu_acl_*: xsknf_amd/csrc/acl.cpp), on the host and
+on the device that was current when it was made.  `firewall_batch` gives the
+verdicts on the device for a UMEM and descriptors that lie there
+(xsknf_gpu_firewall_batch; xsknf_amd/csrc/firewall_device.hip), `firewall_host`
+on one CPU thread (xsknf_gpu_firewall_host: the model the device is held to).
+The verdicts are what route.route_batch consumes; the UMEM is only read.
+"""
+from __future__ import annotations
+
+import ctypes
+import errno
+import os
+
+import numpy as np
+
+from . import _lib
+
+MAX_RULES = _lib.ACL_MAX_RULES
+MAX_SLOTS = _lib.ACL_MAX_SLOTS
+# struct xsknf_gpu_acl_rule: addresses and ports in network order, i.e. the
+# frame's own bytes read as little-endian numbers
+RULE_DTYPE = np.dtype([("saddr", "<u4"), ("daddr", "<u4"), ("sport", "<u2"), ("dport", "<u2"), ("proto", "u1"),
+                       ("pad", "u1", (3,)), ("action", "<i4")])
+assert RULE_DTYPE.itemsize == 20
+
+
+def parse_acl(path) -> np.ndarray:
+    """xsknf_gpu_acl_parse: the reference's ACL text as RULE_DTYPE records (no GPU)."""
+    lib = _lib.load()
+    p = os.fsencode(path)
+    n = ctypes.c_uint32(0)
+    rc = lib.xsknf_gpu_acl_parse(p, None, 0, ctypes.byref(n))
+    if rc not in (0, -errno.ENOSPC):
+        _lib.check(rc, f"xsknf_gpu_acl_parse({path!r})")
+    rules = np.zeros(int(n.value), dtype=RULE_DTYPE)
+    if rules.size:
+        _lib.check(lib.xsknf_gpu_acl_parse(p, rules.ctypes.data, rules.size, ctypes.byref(n)),
+                   f"xsknf_gpu_acl_parse({path!r})")
+    return rules
+
+
+class Acl:
+    """struct xsknf_gpu_acl: the rules as an open-addressing table, on the host
+    and (where the process sees one) on the current device."""
+
+    def __init__(self, handle: int):
+        self._h = handle
+
+    @classmethod
+    def from_rules(cls, rules, slots: int = 0, *, device=None) -> "Acl":
+        """rules: RULE_DTYPE records (any 20-byte records of that layout); the
+        last rule of a key wins.  slots: 0 for the default, or a power of two
+        greater than the number of distinct keys.  device: make it current for
+        the upload (default: the current device)."""
+        r = np.ascontiguousarray(rules)
+        if r.dtype.itemsize != 20 or r.ndim != 1:
+            raise ValueError("rules must be a 1-d array of 20-byte struct xsknf_gpu_acl_rule records")
+        h = ctypes.c_void_p()
+
+        def create():
+            _lib.check(_lib.load().xsknf_gpu_acl_create(ctypes.byref(h), r.ctypes.data if r.size else None, r.size,
+                                                        slots), "xsknf_gpu_acl_create")
+        if device is None:
+            create()
+        else:
+            import torch
+            with torch.cuda.device(device):
+                create()
+        return cls(h.value)
+
+    @classmethod
+    def from_file(cls, path, slots: int = 0, *, device=None) -> "Acl":
+        return cls.from_rules(parse_acl(path), slots, device=device)
+
+    @property
+    def handle(self) -> int:
+        if not self._h:
+            raise ValueError("the ACL is closed")
+        return self._h
+
+    @property
+    def info(self) -> dict:
+        """rules (distinct keys), slots, max_probe, device_bytes."""
+        i = _lib.AclInfo()
+        _lib.check(_lib.load().xsknf_gpu_acl_info(self.handle, ctypes.byref(i)), "xsknf_gpu_acl_info")
+        return {"rules": int(i.rules), "slots": int(i.slots), "max_probe": int(i.max_probe),
+                "device_bytes": int(i.device_bytes)}
+
+    def close(self) -> None:
+        if self._h:
+            h, self._h = self._h, 0
+            _lib.check(_lib.load().xsknf_gpu_acl_destroy(h), "xsknf_gpu_acl_destroy")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # interpreter shutdown
+            pass
+
+
+def firewall_host(umem, descs, acl: Acl) -> np.ndarray:
+    """xsknf_gpu_firewall_host on numpy arrays (a uint8 UMEM, 16-byte descriptor
+    records): one int32 verdict per descriptor."""
+    u = np.ascontiguousarray(umem)
+    if u.dtype != np.uint8:
+        raise ValueError("umem must be uint8")
+    d = np.ascontiguousarray(descs)
+    if d.dtype.itemsize != 16:
+        raise ValueError("descriptors must be struct xdp_desc records (16 bytes)")
+    n = int(d.shape[0])
+    v = np.zeros(n, dtype=np.int32)
+    if n:
+        # (an empty UMEM still needs an address: every descriptor is then outside it)
+        up = u.ctypes.data if u.size else v.ctypes.data
+        _lib.check(_lib.load().xsknf_gpu_firewall_host(up, u.size, d.ctypes.data, n, acl.handle, v.ctypes.data),
+                   "xsknf_gpu_firewall_host")
+    return v
+
+
+def firewall_batch_ptr(umem_ptr: int, umem_size: int, descs_ptr: int, n: int, acl: Acl, verdicts_ptr: int,
+                       stream: int = 0) -> None:
+    """Raw-pointer form of xsknf_gpu_firewall_batch (device pointers; 0 = NULL),
+    on the current device: only enqueues on `stream`."""
+    _lib.check(_lib.load().xsknf_gpu_firewall_batch(
+        ctypes.c_void_p(umem_ptr or None), umem_size, ctypes.c_void_p(descs_ptr or None), n, acl.handle,
+        ctypes.c_void_p(verdicts_ptr or None), ctypes.c_void_p(stream or None)), "xsknf_gpu_firewall_batch")
+
+
+def firewall_batch(umem, descs, acl: Acl, *, device=None):
+    """xsknf_gpu_firewall_batch on torch tensors, on the current stream of their
+    device (the one `acl` was made on): `umem` a contiguous uint8 device tensor,
+    `descs` (n, 2) int64 / (n, 16) uint8, contiguous.  Returns the verdicts as an
+    int32 device tensor of n entries; nothing waits for the stream."""
+    import torch
+
+    if not umem.is_cuda or not descs.is_cuda:
+        raise ValueError("umem and descs must be device tensors (firewall_host is the CPU form)")
+    if umem.dtype != torch.uint8 or not umem.is_contiguous():
+        raise ValueError("umem must be a contiguous uint8 tensor")
+    if not descs.is_contiguous() or descs.numel() * descs.element_size() % 16:
+        raise ValueError("descs must be a contiguous array of 16-byte xdp_desc")
+    n = descs.numel() * descs.element_size() // 16
+    dev = umem.device if device is None else torch.device(device)
+    if umem.device != dev or descs.device != dev:
+        raise ValueError("umem and descs must lie on the firewall's device")
+    with torch.cuda.device(dev):
+        v = torch.empty(n, dtype=torch.int32, device=dev)
+        firewall_batch_ptr(umem.data_ptr() if n else 0, umem.numel(), descs.data_ptr() if n else 0, n, acl,
+                           v.data_ptr() if n else 0, torch.cuda.current_stream(dev).cuda_stream)
+    return v
