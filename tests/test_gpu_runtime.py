@@ -83,12 +83,20 @@ def test_gpu_hook_unaligned(frames):
     assert got[0] == [b for v, b in expected(frames[:6000], iterations=5) if v != -1]
 
 
-@pytest.mark.parametrize("two_phase", [False, True], ids=["one-call", "two-phase"])
+@pytest.mark.parametrize("two_phase,depth", [(False, 1), (True, 1), (True, 4)],
+                         ids=["one-call", "two-phase", "two-phase-depth4"])
 @pytest.mark.parametrize("bind", [(0, 0), (R.XDP_COPY, R.XDP_ZEROCOPY)], ids=["shared-umem", "two-umems"])
-def test_gpu_hook_two_interfaces(frames, bind, two_phase):
+@pytest.mark.parametrize("path", [_lib.PATH_ZEROCOPY, _lib.PATH_STAGED, _lib.PATH_RESIDENT],
+                         ids=["zerocopy", "staged", "resident"])
+def test_gpu_hook_two_interfaces(frames, path, bind, two_phase, depth):
+    """The worker alternates its two interfaces batch by batch, so the ingress
+    (and with it the forward verdict) is each batch's own: on every path the
+    hook accepts, and in two-phase mode with one and with four batches out --
+    with a shared UMEM one context then has batches of ingress 0 and ingress 1
+    in flight together."""
     f0, f1 = frames[:4000], frames[4000:8000]
     cfg = R.make_config(["emu0", "emu1"], batch_size=256, bind=list(bind))
-    got, _, _ = run_loop(cfg, {0: f0, 1: f1}, n_if=2, two_phase=two_phase)
+    got, _, _ = run_loop(cfg, {0: f0, 1: f1}, n_if=2, two_phase=two_phase, depth=depth, path=path)
     e0, e1 = expected(f0, 0, nif=2), expected(f1, 1, nif=2)
     assert sorted(got[0]) == sorted([b for v, b in e0 + e1 if v == 0])
     assert sorted(got[1]) == sorted([b for v, b in e0 + e1 if v == 1])

@@ -123,7 +123,9 @@ class Checksummer:
     def process_batch_ptr(self, umem_ptr: int, umem_size: int, descs_ptr: int, n: int,
                           verdicts_ptr: int, ingress_ifindex: int = 0, stream: int = 0,
                           frame_len_hint: Optional[int] = None) -> None:
-        """Raw-pointer form (device pointers), asynchronous on `stream`."""
+        """Raw-pointer form (device pointers), asynchronous on `stream`.  The
+        options and `ingress_ifindex` are this launch's arguments: launches in
+        flight on other streams, from Checksummers with other options, keep theirs."""
         hint = self.frame_len_hint if frame_len_hint is None else int(frame_len_hint)
         opts = self.csum_opts()
         rc = self._lib.xsknf_gpu_checksum_batch_lens(
@@ -193,7 +195,14 @@ class HostPath:
     array (the worker's mmap), pinned while registered; `process_batch` takes
     host descriptors (DESC_DTYPE) and returns host int32 verdicts, with the check
     bytes rewritten in `umem`.  path: "zerocopy", "staged" or "resident" (zero-copy,
-    every batch through the resident kernel's ring: no launch per batch)."""
+    every batch through the resident kernel's ring: no launch per batch).
+
+    The options and the ingress interface belong to a BATCH, not to the
+    context: `process_batch` and `submit` hand the C call its `opts` and
+    `ingress_ifindex` arguments per call, and batches in flight together may
+    each carry their own (a worker with two interfaces alternates ingress batch
+    by batch, src/xsknf.c:716-742).  `opts` (a `_lib.CsumOpts`: iterations,
+    action, num_interfaces) defaults to the Checksummer's own."""
 
     PATHS = {"zerocopy": _lib.PATH_ZEROCOPY, "staged": _lib.PATH_STAGED, "resident": _lib.PATH_RESIDENT}
 
@@ -219,7 +228,10 @@ class HostPath:
             self.close()
             raise
 
-    def process_batch(self, descs, ingress_ifindex: int = 0, verdicts=None):
+    def process_batch(self, descs, ingress_ifindex: int = 0, verdicts=None,
+                      opts: Optional[_lib.CsumOpts] = None):
+        """One batch, waited for.  `ingress_ifindex` and `opts` are this batch's
+        own (opts None: the Checksummer's)."""
         import numpy as np
 
         if descs.dtype.itemsize != 16 or not descs.flags.c_contiguous:
@@ -229,25 +241,29 @@ class HostPath:
             verdicts = np.empty(n, dtype=np.int32)
         elif verdicts.dtype != np.int32 or verdicts.shape[0] < n or not verdicts.flags.c_contiguous:
             raise ValueError("verdicts must be a contiguous int32 array with >= n entries")
-        opts = self.cs.csum_opts()
+        if opts is None:
+            opts = self.cs.csum_opts()
         _lib.check(self._lib.xsknf_gpu_ctx_process_batch(self._ctx, descs.ctypes.data, n,
                                                          ingress_ifindex, ctypes.byref(opts),
                                                          verdicts.ctypes.data),
                    "xsknf_gpu_ctx_process_batch")
         return verdicts
 
-    def submit(self, descs, verdicts, ingress_ifindex: int = 0) -> int:
+    def submit(self, descs, verdicts, ingress_ifindex: int = 0,
+               opts: Optional[_lib.CsumOpts] = None) -> int:
         """Enqueue a batch (a launched context keeps five pieces in flight, a
         resident one eight; a submit past that waits for the oldest); returns its ticket.  The
         verdicts array and the batch's frames belong to the context until
-        wait(ticket)."""
+        wait(ticket).  `ingress_ifindex` and `opts` are this batch's own (opts
+        None: the Checksummer's); the batches in flight need not share them."""
         if descs.dtype.itemsize != 16 or not descs.flags.c_contiguous:
             raise ValueError("descs must be a contiguous array of 16-byte xdp_desc")
         n = int(descs.shape[0])
         if verdicts.dtype.itemsize != 4 or verdicts.dtype.kind != "i" or verdicts.shape[0] < n \
                 or not verdicts.flags.c_contiguous:
             raise ValueError("verdicts must be a contiguous int32 array with >= n entries")
-        opts = self.cs.csum_opts()
+        if opts is None:
+            opts = self.cs.csum_opts()
         t = ctypes.c_uint64()
         _lib.check(self._lib.xsknf_gpu_ctx_submit(self._ctx, descs.ctypes.data, n, ingress_ifindex,
                                                   ctypes.byref(opts), verdicts.ctypes.data, ctypes.byref(t)),
