@@ -730,6 +730,184 @@ XSKNF_GPU_API int xsknf_gpu_firewall_batch(const uint8_t *umem, uint64_t umem_si
 XSKNF_GPU_API int xsknf_gpu_firewall_host(const uint8_t *umem, uint64_t umem_size,
 		const struct xsknf_gpu_desc *descs, uint32_t n, const struct xsknf_gpu_acl *acl, int32_t *verdicts);
 
+/* ---- the load balancer NF: session table, NAT rewrite, one verdict per frame ---
+ * The reference's L4 load balancer with the per-frame callback
+ * (examples/load_balancer/load_balancer_user.c:396-553, load_balancer.h): a
+ * frame of a known session is rewritten towards its backend or its client; a
+ * frame to a virtual service that has no session picks a backend, stores the
+ * forward and the backward session and is rewritten; everything else passes.
+ * These calls do that for a whole batch, on the device or (the model the device
+ * is held to) on one CPU thread, with exactly the result of the reference's
+ * loop: the frames of a batch are processed in index order against one table,
+ * and a session stored by frame i is seen by every frame j > i.
+ *
+ * Per frame, with f and len as for the firewall (rule 0 gives off), nif =
+ * num_interfaces and PASS = nif > 1 ? (ingress_ifindex + 1) % nif : -1:
+ *   0. not (off <= umem_size && len <= umem_size - off)   -> -1, no byte touched
+ *   1. len < 14                                           -> -1
+ *   2. f[12..13] != 08 00                                 -> PASS
+ *   3. len < 34                                           -> -1
+ *   4. next = 14 + 4 * (f[14] & 15)        (not validated: 0..15)
+ *   5. f[23] == 6: next + 20 > len -> -1;  f[23] == 17: next + 8 > len -> -1;
+ *      any other protocol -> PASS
+ *   6. sid = { saddr f[26..29], daddr f[30..33], sport f[next..next+1],
+ *              dport f[next+2..next+3], proto f[23] } as the values lie in the frame
+ *   7. the session table holds sid: its value `rep` is used, go to 10
+ *   8. no service {daddr, dport, proto}                   -> PASS
+ *   9. backend = the service's record number jhash(sid, 13 bytes, 0) % backends
+ *      (the kernel's jhash, bit-exact); rep = {TO_BACKEND, its addr, port, mac,
+ *      ifindex} is stored under sid; then {TO_CLIENT, daddr, dport, f[6..11],
+ *      ingress_ifindex & 0xffff} is stored under {backend addr, saddr, backend
+ *      port, sport, proto}, replacing the value of a key already there
+ *  10. UPDATE, lines 521-550 in their order: rep.addr and rep.port replace the
+ *      destination address and port (TO_BACKEND) or the source ones; f[6..11] =
+ *      f[0..5], f[0..5] = rep.mac; the IPv4 check f[24..25] and then the L4
+ *      check (f[next+16..] for TCP, f[next+6..] for UDP, a zero UDP check
+ *      included) are updated incrementally with csum_add's end-around carry and
+ *      the two-fold csum_fold of load_balancer.h:54-59, the complements of the
+ *      old check and the old port taken after promotion to 32 bits.  For ihl < 5
+ *      these fields overlap and the order of the reads and writes shows.
+ *      The verdict is rep.ifindex (0..65535).
+ * Multi-byte values are the frame's bytes read little-endian, as the reference
+ * reads them on the hosts it runs on.
+ *
+ * Deviations from the reference: services arrive as arrays (its load_services
+ * leaves ifindex uninitialised for every interface but `local`: line 177
+ * discards the result); a "missing backend" cannot occur (services are built
+ * from their backend lists); where the reference overruns its element pool, an
+ * insert of a new key into a table that holds max_sessions fails and the frame
+ * is still rewritten (the reference's own `goto UPDATE` error path), a failed
+ * forward insert skipping the backward one.  Nothing of its khashmap is kept:
+ * the session table is open addressing over a power-of-two number of 32-byte
+ * slots with the ACL's hash (xsknf_amd/csrc/lb_table.h); jhash only picks the
+ * backend.
+ *
+ * The descriptors of a batch address disjoint byte ranges, which AF_XDP
+ * guarantees; overlapping frames are undefined. */
+#define XSKNF_GPU_LB_MAX_SERVICES 1024u       /* MAX_SERVICES, load_balancer.h */
+#define XSKNF_GPU_LB_MAX_BACKENDS 131072u     /* MAX_BACKENDS */
+#define XSKNF_GPU_LB_MAX_SESSIONS 2000000u    /* MAX_SESSIONS */
+#define XSKNF_GPU_LB_MAX_SLOTS (1u << 24)
+#define XSKNF_GPU_LB_MAX_BATCH (1u << 24)     /* frames per xsknf_gpu_lb_batch */
+#define XSKNF_GPU_LB_TO_CLIENT 0              /* enum direction, load_balancer.h */
+#define XSKNF_GPU_LB_TO_BACKEND 1
+#define XSKNF_GPU_LB_HOST_TABLE 0             /* xsknf_gpu_lb_sessions_dump's `which` */
+#define XSKNF_GPU_LB_DEVICE_TABLE 1
+/* stats: [0] frames, [1] rewritten (reached UPDATE), [2] passed (a PASS rule,
+ * whatever its value), [3] dropped (-1 by rules 0-5), [4] sessions created,
+ * [5] inserts failed, [6] batches that took the ordered path, [7] reserved (0) */
+#define XSKNF_GPU_LB_STATS 8
+
+/* One backend of one service.  A service's backend number is the record's order
+ * among that service's records (the reference's file order). */
+struct xsknf_gpu_lb_backend {
+	uint32_t vaddr;          /* the service: network order */
+	uint16_t vport;          /* network order */
+	uint8_t proto;           /* 6 or 17 */
+	uint8_t pad;             /* ignored */
+	uint32_t addr;           /* the backend: network order */
+	uint16_t port;           /* network order */
+	uint8_t mac[6];
+	uint16_t ifindex;        /* the verdict of a frame sent to this backend */
+	uint8_t pad2[2];         /* ignored */
+};
+
+struct xsknf_gpu_lb_session_key {   /* struct session_id, padded to 16 bytes */
+	uint32_t saddr, daddr;   /* network order */
+	uint16_t sport, dport;   /* network order */
+	uint8_t proto;           /* 6 or 17 */
+	uint8_t pad[3];          /* ignored; 0 in a dump */
+};
+
+struct xsknf_gpu_lb_session_value {   /* struct replace_info in 16 bytes */
+	uint32_t addr;
+	uint16_t port;
+	uint16_t ifindex;
+	uint8_t mac[6];
+	uint8_t dir;             /* XSKNF_GPU_LB_TO_CLIENT or _TO_BACKEND */
+	uint8_t pad;             /* ignored; 0 in a dump */
+};
+
+struct xsknf_gpu_lb;         /* opaque */
+
+struct xsknf_gpu_lb_info {
+	uint32_t services, backends;
+	uint32_t max_sessions, slots;
+	uint32_t host_sessions;      /* stored in the host table */
+	uint32_t device_sessions;    /* stored in the device table (synchronizes the device) */
+	uint64_t device_bytes;       /* 0: built where no device was visible */
+};
+
+/* Build the service and backend tables from n records on the calling thread
+ * (deterministic) and upload them to the current device together with an empty
+ * session table of `slots` slots that holds at most max_sessions sessions; an
+ * independent, equally sized host session table serves xsknf_gpu_lb_host.
+ * slots == 0: the smallest power of two >= 2 * max_sessions, at least 64;
+ * otherwise a power of two >= 2 * max_sessions, at most XSKNF_GPU_LB_MAX_SLOTS.
+ * In a process that sees no HIP device the object is host-only (device_bytes
+ * 0) and xsknf_gpu_lb_batch returns -ENODEV for it.  -EINVAL: a NULL lb_out, a
+ * NULL backends with n > 0, a record whose proto is neither 6 nor 17, more than
+ * XSKNF_GPU_LB_MAX_BACKENDS records or XSKNF_GPU_LB_MAX_SERVICES services,
+ * max_sessions above XSKNF_GPU_LB_MAX_SESSIONS, a bad slots.  -ENOMEM; -EIO on
+ * a HIP error (xsknf_gpu_last_error()). */
+XSKNF_GPU_API int xsknf_gpu_lb_create(struct xsknf_gpu_lb **lb_out, const struct xsknf_gpu_lb_backend *backends,
+		uint32_t n, uint32_t max_sessions, uint32_t slots);
+XSKNF_GPU_API int xsknf_gpu_lb_info(const struct xsknf_gpu_lb *lb, struct xsknf_gpu_lb_info *info);
+/* Free the tables on the device and the host (no batch may be in flight). */
+XSKNF_GPU_API int xsknf_gpu_lb_destroy(struct xsknf_gpu_lb *lb);
+
+/* Store n sessions in BOTH session tables, in order, a later value replacing an
+ * earlier one of the same key (the reference's --passthrough and --local
+ * modes).  Call it only with no batch in flight: it waits for the device and
+ * rewrites the device table from the host.  Everything is validated before
+ * anything is stored: -EINVAL for a NULL argument with n > 0, a dir other than
+ * 0 and 1 or a proto other than 6 and 17.  -ENOSPC when a new key meets a table
+ * that holds max_sessions: the sessions before it stay stored. */
+XSKNF_GPU_API int xsknf_gpu_lb_sessions_put(struct xsknf_gpu_lb *lb, const struct xsknf_gpu_lb_session_key *keys,
+		const struct xsknf_gpu_lb_session_value *values, uint32_t n);
+/* Every session of the host table (which == XSKNF_GPU_LB_HOST_TABLE) or the
+ * device table (_DEVICE_TABLE; waits for the device), ascending by {saddr, daddr,
+ * sport | dport << 16, proto} compared as numbers in that order.  *n_out is the
+ * table's count; at most cap records are written (-ENOSPC if cap is smaller).
+ * For tests and monitoring.  -ENODEV for the device table of a host-only object. */
+XSKNF_GPU_API int xsknf_gpu_lb_sessions_dump(const struct xsknf_gpu_lb *lb, int which,
+		struct xsknf_gpu_lb_session_key *keys, struct xsknf_gpu_lb_session_value *values, uint32_t cap,
+		uint32_t *n_out);
+
+/* Bytes of device workspace a batch of n frames needs (16-byte aligned, the
+ * caller's, as for the router; its contents mean nothing between calls).
+ * -EINVAL for a NULL bytes or n > XSKNF_GPU_LB_MAX_BATCH. */
+XSKNF_GPU_API int xsknf_gpu_lb_workspace(uint32_t n, uint64_t *bytes);
+
+/* One batch on the current device (the one lb was created on), asynchronously
+ * on `stream`; nothing is read back by the call.  umem, descs (16-byte aligned),
+ * verdicts (4-byte aligned), workspace (16-byte aligned) and stats_dev (8
+ * uint64, 8-byte aligned, zeroed on the stream first) are device memory.
+ * Written: verdicts[0 .. n), the bytes rule 10 changes in the frames that reach
+ * UPDATE -- by byte and aligned 2-byte stores that lie inside the frame, so a
+ * neighbour that shares a word with it is never touched --, the device session
+ * table, the workspace and stats_dev.  Nothing else.  Frame bytes are read as
+ * aligned 4-byte words that each hold a byte of the frame (see
+ * xsknf_gpu_firewall_batch).
+ * Batches whose sessions can be created independently run one lane per frame;
+ * a batch in which two flows store the same session key, a stored key would
+ * replace an older session, or the new sessions do not all fit is run by the
+ * ordered path, ONE lane that walks the loop: exact, and slow (stats[6]).
+ * n == 0 succeeds with nothing touched.  -EINVAL, before any GPU call: a NULL lb
+ * or stats_dev, a misaligned pointer, n > XSKNF_GPU_LB_MAX_BATCH, and with n > 0
+ * a NULL umem, descs, verdicts or workspace or workspace_bytes below
+ * xsknf_gpu_lb_workspace(n).  -ENODEV for a host-only lb.  -EIO on a HIP error,
+ * with xsknf_gpu_last_error() set. */
+XSKNF_GPU_API int xsknf_gpu_lb_batch(uint8_t *umem, uint64_t umem_size, const struct xsknf_gpu_desc *descs,
+		uint32_t n, uint32_t ingress_ifindex, uint32_t num_interfaces, struct xsknf_gpu_lb *lb,
+		int32_t *verdicts, void *workspace, uint64_t workspace_bytes, uint64_t *stats_dev, void *stream);
+/* The same on host arrays over the host session table: one thread, the loop
+ * above with byte reads and writes in the reference's order, no GPU call and no
+ * alignment asked.  stats (8 uint64, may be NULL) is overwritten. */
+XSKNF_GPU_API int xsknf_gpu_lb_host(uint8_t *umem, uint64_t umem_size, const struct xsknf_gpu_desc *descs,
+		uint32_t n, uint32_t ingress_ifindex, uint32_t num_interfaces, struct xsknf_gpu_lb *lb,
+		int32_t *verdicts, uint64_t *stats);
+
 /* Text of the last HIP error seen by this library, on any thread (a copy
  * private to the calling thread). */
 XSKNF_GPU_API const char *xsknf_gpu_last_error(void);

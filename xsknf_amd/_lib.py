@@ -63,7 +63,22 @@ EXPORTED_SYMBOLS = (
     "xsknf_gpu_acl_destroy",
     "xsknf_gpu_firewall_batch",
     "xsknf_gpu_firewall_host",
+    "xsknf_gpu_lb_create",
+    "xsknf_gpu_lb_info",
+    "xsknf_gpu_lb_destroy",
+    "xsknf_gpu_lb_sessions_put",
+    "xsknf_gpu_lb_sessions_dump",
+    "xsknf_gpu_lb_workspace",
+    "xsknf_gpu_lb_batch",
+    "xsknf_gpu_lb_host",
 )
+
+LB_MAX_SERVICES = 1024      # XSKNF_GPU_LB_MAX_SERVICES
+LB_MAX_BACKENDS = 131072    # XSKNF_GPU_LB_MAX_BACKENDS
+LB_MAX_SESSIONS = 2000000   # XSKNF_GPU_LB_MAX_SESSIONS
+LB_MAX_SLOTS = 1 << 24      # XSKNF_GPU_LB_MAX_SLOTS
+LB_MAX_BATCH = 1 << 24      # XSKNF_GPU_LB_MAX_BATCH
+LB_STATS = 8                # XSKNF_GPU_LB_STATS
 
 ACL_MAX_RULES = 1000000     # XSKNF_GPU_ACL_MAX_RULES
 ACL_MAX_SLOTS = 1 << 24     # XSKNF_GPU_ACL_MAX_SLOTS
@@ -135,6 +150,14 @@ class AclInfo(ctypes.Structure):
 
     _fields_ = [("rules", ctypes.c_uint32), ("slots", ctypes.c_uint32), ("max_probe", ctypes.c_uint32),
                 ("reserved", ctypes.c_uint32), ("device_bytes", ctypes.c_uint64)]
+
+
+class LbInfo(ctypes.Structure):
+    """struct xsknf_gpu_lb_info (include/xsknf_gpu.h)."""
+
+    _fields_ = [("services", ctypes.c_uint32), ("backends", ctypes.c_uint32), ("max_sessions", ctypes.c_uint32),
+                ("slots", ctypes.c_uint32), ("host_sessions", ctypes.c_uint32), ("device_sessions", ctypes.c_uint32),
+                ("device_bytes", ctypes.c_uint64)]
 
 
 class XsknfGpuError(RuntimeError):
@@ -295,6 +318,23 @@ def load() -> ctypes.CDLL:
     lib.xsknf_gpu_firewall_batch.argtypes = [vp, u64, vp, ctypes.c_uint32, vp, vp, vp]
     lib.xsknf_gpu_firewall_host.restype = ctypes.c_int
     lib.xsknf_gpu_firewall_host.argtypes = [vp, u64, vp, ctypes.c_uint32, vp, vp]
+    u32 = ctypes.c_uint32
+    lib.xsknf_gpu_lb_create.restype = ctypes.c_int
+    lib.xsknf_gpu_lb_create.argtypes = [ctypes.POINTER(vp), vp, u32, u32, u32]
+    lib.xsknf_gpu_lb_info.restype = ctypes.c_int
+    lib.xsknf_gpu_lb_info.argtypes = [vp, ctypes.POINTER(LbInfo)]
+    lib.xsknf_gpu_lb_destroy.restype = ctypes.c_int
+    lib.xsknf_gpu_lb_destroy.argtypes = [vp]
+    lib.xsknf_gpu_lb_sessions_put.restype = ctypes.c_int
+    lib.xsknf_gpu_lb_sessions_put.argtypes = [vp, vp, vp, u32]
+    lib.xsknf_gpu_lb_sessions_dump.restype = ctypes.c_int
+    lib.xsknf_gpu_lb_sessions_dump.argtypes = [vp, ctypes.c_int, vp, vp, u32, ctypes.POINTER(u32)]
+    lib.xsknf_gpu_lb_workspace.restype = ctypes.c_int
+    lib.xsknf_gpu_lb_workspace.argtypes = [u32, ctypes.POINTER(u64)]
+    lib.xsknf_gpu_lb_batch.restype = ctypes.c_int
+    lib.xsknf_gpu_lb_batch.argtypes = [vp, u64, vp, u32, u32, u32, vp, vp, vp, u64, vp, vp]
+    lib.xsknf_gpu_lb_host.restype = ctypes.c_int
+    lib.xsknf_gpu_lb_host.argtypes = [vp, u64, vp, u32, u32, u32, vp, vp, vp]
     lib.xsknf_gpu_pool_guard_trips.restype = ctypes.c_int
     lib.xsknf_gpu_pool_guard_trips.argtypes = [ctypes.POINTER(ctypes.c_uint32), ctypes.c_int]
     _lib = lib

@@ -1,0 +1,210 @@
+"""The load balancer NF: session table, NAT rewrite, one verdict per frame.
+
+The reference's L4 load balancer with the per-frame callback
+(examples/load_balancer/load_balancer_user.c:396-553): a frame of a known
+session is rewritten towards its backend or its client, a frame to a virtual
+service without a session picks a backend, stores the forward and the backward
+session and is rewritten, everything else passes.  The rules per frame are in
+include/xsknf_gpu.h ("the load balancer NF").
+
+`LoadBalancer` holds the services, the backends and two independent session
+tables (xsknf_gpu_lb_*: xsknf_amd/csrc/lb.cpp), one on the host and one on the
+device that was current when it was made.  `lb_batch` runs a batch on the device
+for a UMEM and descriptors that lie there (xsknf_gpu_lb_batch;
+xsknf_amd/csrc/lb_device.hip), `lb_host` on one CPU thread (xsknf_gpu_lb_host:
+the model the device is held to).  Both rewrite the UMEM in place; the verdicts
+are what route.route_batch consumes.
+"""
+from __future__ import annotations
+
+import ctypes
+import errno
+
+import numpy as np
+
+from . import _lib
+
+MAX_SERVICES = _lib.LB_MAX_SERVICES
+MAX_BACKENDS = _lib.LB_MAX_BACKENDS
+MAX_SESSIONS = _lib.LB_MAX_SESSIONS
+MAX_SLOTS = _lib.LB_MAX_SLOTS
+MAX_BATCH = _lib.LB_MAX_BATCH
+TO_CLIENT, TO_BACKEND = 0, 1
+HOST_TABLE, DEVICE_TABLE = 0, 1
+# the words of a batch's stats (XSKNF_GPU_LB_STATS)
+LB_STATS = ("frames", "rewritten", "passed", "dropped", "sessions_created", "inserts_failed", "ordered_batches",
+            "reserved")
+assert len(LB_STATS) == _lib.LB_STATS
+# addresses and ports in network order, i.e. the frame's own bytes read as
+# little-endian numbers
+BACKEND_DTYPE = np.dtype([("vaddr", "<u4"), ("vport", "<u2"), ("proto", "u1"), ("pad", "u1"), ("addr", "<u4"),
+                          ("port", "<u2"), ("mac", "u1", (6,)), ("ifindex", "<u2"), ("pad2", "u1", (2,))])
+KEY_DTYPE = np.dtype([("saddr", "<u4"), ("daddr", "<u4"), ("sport", "<u2"), ("dport", "<u2"), ("proto", "u1"),
+                      ("pad", "u1", (3,))])
+VALUE_DTYPE = np.dtype([("addr", "<u4"), ("port", "<u2"), ("ifindex", "<u2"), ("mac", "u1", (6,)), ("dir", "u1"),
+                        ("pad", "u1")])
+assert BACKEND_DTYPE.itemsize == 24 and KEY_DTYPE.itemsize == 16 and VALUE_DTYPE.itemsize == 16
+
+
+def _records(a, itemsize: int, what: str) -> np.ndarray:
+    r = np.ascontiguousarray(a)
+    if r.dtype.itemsize != itemsize or r.ndim != 1:
+        raise ValueError(f"{what} must be a 1-d array of {itemsize}-byte records")
+    return r
+
+
+class LoadBalancer:
+    """struct xsknf_gpu_lb: services, backends and the session tables, on the
+    host and (where the process sees one) on the current device."""
+
+    def __init__(self, handle: int):
+        self._h = handle
+
+    @classmethod
+    def from_backends(cls, backends, max_sessions: int = MAX_SESSIONS, slots: int = 0, *, device=None) -> "LoadBalancer":
+        """backends: BACKEND_DTYPE records, one per backend of a service; a
+        service's backend number is the record's order among that service's
+        records.  max_sessions: what a session table may hold.  slots: 0 for
+        the default, or a power of two >= 2 * max_sessions.  device: make it
+        current for the upload (default: the current device)."""
+        r = _records(backends, 24, "backends")
+        h = ctypes.c_void_p()
+
+        def create():
+            _lib.check(_lib.load().xsknf_gpu_lb_create(ctypes.byref(h), r.ctypes.data if r.size else None, r.size,
+                                                       max_sessions, slots), "xsknf_gpu_lb_create")
+        if device is None:
+            create()
+        else:
+            import torch
+            with torch.cuda.device(device):
+                create()
+        return cls(h.value)
+
+    @property
+    def handle(self) -> int:
+        if not self._h:
+            raise ValueError("the load balancer is closed")
+        return self._h
+
+    @property
+    def info(self) -> dict:
+        """services, backends, max_sessions, slots, host_sessions, device_sessions, device_bytes."""
+        i = _lib.LbInfo()
+        _lib.check(_lib.load().xsknf_gpu_lb_info(self.handle, ctypes.byref(i)), "xsknf_gpu_lb_info")
+        return {k: int(getattr(i, k)) for k, _ in _lib.LbInfo._fields_}
+
+    def sessions_put(self, keys, values) -> None:
+        """xsknf_gpu_lb_sessions_put: KEY_DTYPE / VALUE_DTYPE records into both
+        session tables, in order.  Only with no batch in flight."""
+        k, v = _records(keys, 16, "keys"), _records(values, 16, "values")
+        if k.size != v.size:
+            raise ValueError("one value per key")
+        _lib.check(_lib.load().xsknf_gpu_lb_sessions_put(self.handle, k.ctypes.data if k.size else None,
+                                                         v.ctypes.data if v.size else None, k.size),
+                   "xsknf_gpu_lb_sessions_put")
+
+    def sessions_dump(self, which: int = HOST_TABLE):
+        """xsknf_gpu_lb_sessions_dump: (keys, values) of the host or the device
+        table, ascending by key.  Waits for the device."""
+        lib = _lib.load()
+        n = ctypes.c_uint32(0)
+        rc = lib.xsknf_gpu_lb_sessions_dump(self.handle, which, None, None, 0, ctypes.byref(n))
+        if rc not in (0, -errno.ENOSPC):
+            _lib.check(rc, "xsknf_gpu_lb_sessions_dump")
+        k, v = np.zeros(int(n.value), dtype=KEY_DTYPE), np.zeros(int(n.value), dtype=VALUE_DTYPE)
+        if k.size:
+            _lib.check(lib.xsknf_gpu_lb_sessions_dump(self.handle, which, k.ctypes.data, v.ctypes.data, k.size,
+                                                      ctypes.byref(n)), "xsknf_gpu_lb_sessions_dump")
+        return k, v
+
+    def close(self) -> None:
+        if self._h:
+            h, self._h = self._h, 0
+            _lib.check(_lib.load().xsknf_gpu_lb_destroy(h), "xsknf_gpu_lb_destroy")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # interpreter shutdown
+            pass
+
+
+def lb_workspace(n: int) -> int:
+    """xsknf_gpu_lb_workspace: the bytes of device workspace a batch of n frames needs."""
+    b = ctypes.c_uint64(0)
+    _lib.check(_lib.load().xsknf_gpu_lb_workspace(n, ctypes.byref(b)), "xsknf_gpu_lb_workspace")
+    return int(b.value)
+
+
+def lb_host(umem, descs, lb: LoadBalancer, ingress_ifindex: int = 0, num_interfaces: int = 1):
+    """xsknf_gpu_lb_host on numpy arrays: `umem` (uint8, contiguous, writable)
+    is rewritten IN PLACE over the host session table.  Returns (verdicts int32,
+    stats uint64[8])."""
+    if not (isinstance(umem, np.ndarray) and umem.dtype == np.uint8 and umem.flags.c_contiguous
+            and umem.flags.writeable):
+        raise ValueError("umem must be a writable contiguous uint8 array (it is rewritten in place)")
+    d = np.ascontiguousarray(descs)
+    if d.dtype.itemsize != 16:
+        raise ValueError("descriptors must be struct xdp_desc records (16 bytes)")
+    n = int(d.shape[0])
+    v = np.zeros(n, dtype=np.int32)
+    st = np.zeros(_lib.LB_STATS, dtype=np.uint64)
+    # (an empty UMEM still needs an address: every descriptor is then outside it)
+    up = umem.ctypes.data if umem.size else st.ctypes.data
+    _lib.check(_lib.load().xsknf_gpu_lb_host(up if n else None, umem.size, d.ctypes.data if n else None, n,
+                                             ingress_ifindex, num_interfaces, lb.handle,
+                                             v.ctypes.data if n else None, st.ctypes.data), "xsknf_gpu_lb_host")
+    return v, st
+
+
+def lb_batch_ptr(umem_ptr: int, umem_size: int, descs_ptr: int, n: int, ingress_ifindex: int, num_interfaces: int,
+                 lb: LoadBalancer, verdicts_ptr: int, workspace_ptr: int, workspace_bytes: int, stats_ptr: int,
+                 stream: int = 0) -> None:
+    """Raw-pointer form of xsknf_gpu_lb_batch (device pointers; 0 = NULL), on
+    the current device: only enqueues on `stream`."""
+    _lib.check(_lib.load().xsknf_gpu_lb_batch(
+        ctypes.c_void_p(umem_ptr or None), umem_size, ctypes.c_void_p(descs_ptr or None), n, ingress_ifindex,
+        num_interfaces, lb.handle, ctypes.c_void_p(verdicts_ptr or None), ctypes.c_void_p(workspace_ptr or None),
+        workspace_bytes, ctypes.c_void_p(stats_ptr or None), ctypes.c_void_p(stream or None)), "xsknf_gpu_lb_batch")
+
+
+def lb_batch(umem, descs, lb: LoadBalancer, ingress_ifindex: int = 0, num_interfaces: int = 1, *, workspace=None,
+             device=None):
+    """xsknf_gpu_lb_batch on torch tensors, on the current stream of their
+    device (the one `lb` was made on): `umem` a contiguous uint8 device tensor,
+    rewritten IN PLACE; `descs` (n, 2) int64 / (n, 16) uint8, contiguous;
+    `workspace` a uint8 device tensor of at least lb_workspace(n) bytes
+    (default: a new one).  Returns (verdicts int32[n], stats int64[8]) as device
+    tensors; nothing waits for the stream."""
+    import torch
+
+    if not umem.is_cuda or not descs.is_cuda:
+        raise ValueError("umem and descs must be device tensors (lb_host is the CPU form)")
+    if umem.dtype != torch.uint8 or not umem.is_contiguous():
+        raise ValueError("umem must be a contiguous uint8 tensor")
+    if not descs.is_contiguous() or descs.numel() * descs.element_size() % 16:
+        raise ValueError("descs must be a contiguous array of 16-byte xdp_desc")
+    n = descs.numel() * descs.element_size() // 16
+    dev = umem.device if device is None else torch.device(device)
+    if umem.device != dev or descs.device != dev:
+        raise ValueError("umem and descs must lie on the load balancer's device")
+    need = lb_workspace(n)
+    with torch.cuda.device(dev):
+        if workspace is None:
+            workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+        elif (workspace.device != dev or workspace.dtype != torch.uint8 or not workspace.is_contiguous()
+              or workspace.numel() < need):
+            raise ValueError(f"workspace must be a contiguous uint8 tensor of >= {need} bytes on the device")
+        v = torch.empty(n, dtype=torch.int32, device=dev)
+        st = torch.zeros(_lib.LB_STATS, dtype=torch.int64, device=dev)
+        lb_batch_ptr(umem.data_ptr() if n else 0, umem.numel(), descs.data_ptr() if n else 0, n, ingress_ifindex,
+                     num_interfaces, lb, v.data_ptr() if n else 0, workspace.data_ptr() if n else 0,
+                     workspace.numel(), st.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    return v, st
