@@ -795,7 +795,8 @@ XSKNF_GPU_API int xsknf_gpu_firewall_host(const uint8_t *umem, uint64_t umem_siz
 #define XSKNF_GPU_LB_DEVICE_TABLE 1
 /* stats: [0] frames, [1] rewritten (reached UPDATE), [2] passed (a PASS rule,
  * whatever its value), [3] dropped (-1 by rules 0-5), [4] sessions created,
- * [5] inserts failed, [6] batches that took the ordered path, [7] reserved (0) */
+ * [5] inserts failed, [6] batches that took the ordered path, [7] 0 (the lbfw
+ * NF below: frames its ACL decided) */
 #define XSKNF_GPU_LB_STATS 8
 
 /* One backend of one service.  A service's backend number is the record's order
@@ -907,6 +908,44 @@ XSKNF_GPU_API int xsknf_gpu_lb_batch(uint8_t *umem, uint64_t umem_size, const st
 XSKNF_GPU_API int xsknf_gpu_lb_host(uint8_t *umem, uint64_t umem_size, const struct xsknf_gpu_desc *descs,
 		uint32_t n, uint32_t ingress_ifindex, uint32_t num_interfaces, struct xsknf_gpu_lb *lb,
 		int32_t *verdicts, uint64_t *stats);
+
+/* ---- the lbfw NF: the firewall's ACL as a gate in front of the load balancer ---
+ * The reference's examples/lbfw (lbfw_user.c:420-594): the load balancer's
+ * per-frame function with exactly two differences.  Everything else -- rules
+ * 0-10, the loop's order, the two-fold csum_fold, the byte order for ihl < 5,
+ * the full-table deviation, the store widths -- is the load balancer's above.
+ *   PASS = (ingress_ifindex + 1) % nif at all three places (rules 2, 5, 8):
+ *        one interface passes to interface 0, not -1.  nif == 0, where the
+ *        reference divides by zero, is -EINVAL before any work.
+ *   6a.  between rules 6 and 7: if the ACL holds sid, the verdict is that
+ *        rule's action -- any int32, an action of 0 being a hit like any other
+ *        -- the frame is not touched, and no session is looked up or stored.
+ *        A sid the ACL does not hold goes on to rules 7-10.
+ * The gate is the reference's MODE_AF_XDP.  In its MODE_COMBINED the XDP
+ * program has applied the ACL already and the function skips it: here that is
+ * acl == NULL (rule 6a never applies; PASS is still lbfw's).
+ *
+ * The calls work on the existing objects: an xsknf_gpu_acl (only read) and an
+ * xsknf_gpu_lb, whose session tables are the ones xsknf_gpu_lb_batch and
+ * xsknf_gpu_lb_host use: calls of both NFs on one object may alternate on one
+ * stream.  The workspace is xsknf_gpu_lb_workspace(n).  stats are the load
+ * balancer's with [7] = the frames the ACL decided, which count in none of
+ * [1], [2], [3]: [0] = [1] + [2] + [3] + [7].
+ *
+ * xsknf_gpu_lbfw_batch: arguments, alignment, what is written, the ordered
+ * path, n == 0 and the errors are xsknf_gpu_lb_batch's, on the current device
+ * (the one BOTH objects were created on); a frame the gate decides is never
+ * part of a reason for the ordered path.  In addition -EINVAL for
+ * num_interfaces == 0 (first of all) and -ENODEV for an lb or a non-NULL acl
+ * without a device half.  xsknf_gpu_lbfw_host: as xsknf_gpu_lb_host, over the
+ * host session table and the ACL's host copy; -EINVAL for num_interfaces == 0. */
+XSKNF_GPU_API int xsknf_gpu_lbfw_batch(uint8_t *umem, uint64_t umem_size, const struct xsknf_gpu_desc *descs,
+		uint32_t n, uint32_t ingress_ifindex, uint32_t num_interfaces, const struct xsknf_gpu_acl *acl /* may be NULL */,
+		struct xsknf_gpu_lb *lb, int32_t *verdicts, void *workspace, uint64_t workspace_bytes, uint64_t *stats_dev,
+		void *stream);
+XSKNF_GPU_API int xsknf_gpu_lbfw_host(uint8_t *umem, uint64_t umem_size, const struct xsknf_gpu_desc *descs,
+		uint32_t n, uint32_t ingress_ifindex, uint32_t num_interfaces, const struct xsknf_gpu_acl *acl /* may be NULL */,
+		struct xsknf_gpu_lb *lb, int32_t *verdicts, uint64_t *stats);
 
 /* Text of the last HIP error seen by this library, on any thread (a copy
  * private to the calling thread). */

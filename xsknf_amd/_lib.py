@@ -71,6 +71,8 @@ EXPORTED_SYMBOLS = (
     "xsknf_gpu_lb_workspace",
     "xsknf_gpu_lb_batch",
     "xsknf_gpu_lb_host",
+    "xsknf_gpu_lbfw_batch",
+    "xsknf_gpu_lbfw_host",
 )
 
 LB_MAX_SERVICES = 1024      # XSKNF_GPU_LB_MAX_SERVICES
@@ -335,6 +337,11 @@ def load() -> ctypes.CDLL:
     lib.xsknf_gpu_lb_batch.argtypes = [vp, u64, vp, u32, u32, u32, vp, vp, vp, u64, vp, vp]
     lib.xsknf_gpu_lb_host.restype = ctypes.c_int
     lib.xsknf_gpu_lb_host.argtypes = [vp, u64, vp, u32, u32, u32, vp, vp, vp]
+    # the lbfw NF (an ACL, or NULL, in front of the load balancer's arguments)
+    lib.xsknf_gpu_lbfw_batch.restype = ctypes.c_int
+    lib.xsknf_gpu_lbfw_batch.argtypes = [vp, u64, vp, u32, u32, u32, vp, vp, vp, vp, u64, vp, vp]
+    lib.xsknf_gpu_lbfw_host.restype = ctypes.c_int
+    lib.xsknf_gpu_lbfw_host.argtypes = [vp, u64, vp, u32, u32, u32, vp, vp, vp, vp]
     lib.xsknf_gpu_pool_guard_trips.restype = ctypes.c_int
     lib.xsknf_gpu_pool_guard_trips.argtypes = [ctypes.POINTER(ctypes.c_uint32), ctypes.c_int]
     _lib = lib

@@ -55,6 +55,22 @@ XSKNF_HD inline int32_t acl_lookup(const AclKey *keys, const int32_t *actions, u
   return 0;
 }
 
+// The slot of key {a, b, c, p} (p != 0), or kAclNone: for a caller to whom an
+// action of 0 is a hit like any other (the lbfw NF's gate).
+constexpr uint32_t kAclNone = 0xffffffffu;
+XSKNF_HD inline uint32_t acl_find(const AclKey *keys, uint32_t slots, uint32_t a, uint32_t b, uint32_t c,
+                                  uint32_t p) {
+  const uint32_t mask = slots - 1;
+  uint32_t s = acl_hash(a, b, c, p) & mask;
+  for (uint32_t i = 0; i < slots; ++i) {   // bounded whatever the table holds
+    const AclKey k = keys[s];
+    if (k.p == 0) return kAclNone;
+    if (k.a == a && k.b == b && k.c == c && k.p == p) return s;
+    s = (s + 1) & mask;
+  }
+  return kAclNone;
+}
+
 }  // namespace xsknf_gpu
 
 // The object behind struct xsknf_gpu_acl: the table on the host and, unless

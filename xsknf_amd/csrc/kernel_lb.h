@@ -1,5 +1,7 @@
-// kernel_lb.h -- the load balancer's device kernels.  Part of lb_device.hip's
-// translation unit (none of checksummer.hip's).
+// kernel_lb.h -- the load balancer's device kernels, and the lbfw NF's: the same
+// four launches with the batch's own PASS value (Args::pass) and, in
+// lb_propose<true>, the ACL gate.  Part of lb_device.hip's translation unit
+// (none of checksummer.hip's).
 //
 // A batch must give exactly what the reference's loop gives, frame after frame
 // against one table, without one thread doing the work.  Four launches, all
@@ -87,7 +89,9 @@ struct Args {
   uint32_t *state;
   uint32_t *prop;
   unsigned long long *stats;
-  uint32_t n, ingress, nif, stage_slots;
+  uint32_t n, ingress, stage_slots;
+  int32_t pass;        // the batch's PASS verdict (the NF's own: lb_table.h), computed once on the host
+  lb::Gate gate;       // lbfw's ACL on the device; read by lb_propose<true> alone
 };
 
 __device__ __forceinline__ uint32_t ld_agent(const uint32_t *p) {
@@ -160,6 +164,14 @@ __device__ __forceinline__ void flush(const Args &a, uint32_t *c) {
                            __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// kGate: the lbfw NF (rule 6a).  A candidate whose sid the ACL holds gets the
+// rule's action as its verdict here and is kDone: no table is touched for it,
+// nothing is proposed, and the later launches never see it.  The gate reads
+// only the frame's own sid and the immutable ACL, so it needs no order.  The
+// two probes run one after the other: a variant that issued the ACL's and the
+// session table's home-slot loads together measured no faster.
+// The load balancer's instantiation, kGate false, carries none of this.
+template <bool kGate>
 __global__ __launch_bounds__(kThreads) void lb_propose(const Args a) {
   __shared__ uint32_t c[lb::kStats];
   if (threadIdx.x < lb::kStats) c[threadIdx.x] = 0;
@@ -188,7 +200,7 @@ __global__ __launch_bounds__(kThreads) void lb_propose(const Args a) {
       }
     }
     if (!cand) {
-      if (pass) verdict = lb::pass_verdict(a.ingress, a.nif);
+      if (pass) verdict = a.pass;
       count(c, pass ? lb::kPassed : lb::kDropped);
       a.verdicts[f] = verdict;
       a.state[f] = kDone;
@@ -196,6 +208,15 @@ __global__ __launch_bounds__(kThreads) void lb_propose(const Args a) {
     }
     const uint32_t shape = (proto == 6 ? 1u << 29 : 0u) | ((e >> 16) & 15) << 25;
     const lb::Key sid = {sa, da, ld_bytes(a.umem, off + next, 4), proto};    // rule 6
+    if constexpr (kGate) {
+      const uint32_t g = acl_find(a.gate.keys, a.gate.slots, sid.a, sid.b, sid.c, sid.p);
+      if (g != kAclNone) {                                                   // rule 6a
+        count(c, lb::kGated);
+        a.verdicts[f] = a.gate.actions[g];
+        a.state[f] = kDone;
+        continue;
+      }
+    }
     const uint32_t slot = lb::find(a.t.keys, a.t.slots, sid);                // rule 7
     if (slot != lb::kNone) {
       a.state[f] = kHit | shape | slot;
@@ -292,7 +313,7 @@ __global__ __launch_bounds__(kThreads) void lb_apply(const Args a) {
       }
     }
     if (!have) {
-      a.verdicts[f] = lb::pass_verdict(a.ingress, a.nif);
+      a.verdicts[f] = a.pass;
       count(c, lb::kPassed);
       continue;
     }
@@ -350,11 +371,12 @@ __global__ __launch_bounds__(64) void lb_ordered(const Args a) {
     return;
   }
   a.stats[lb::kOrdered] += 1;
+  const lb::Gate none = {nullptr, nullptr, 0};   // (a frame the gate decided is kDone)
   for (uint32_t f = 0; f < a.n; ++f) {
     if ((a.state[f] & kClassMask) == kDone) continue;
     const uint4 d = a.descs[f];
     const uint64_t off = desc_offset(static_cast<uint64_t>(d.x) | static_cast<uint64_t>(d.y) << 32);
-    a.verdicts[f] = lb::frame(a.t, a.umem + off, d.z, a.ingress, a.nif, a.stats);
+    a.verdicts[f] = lb::frame(a.t, none, a.umem + off, d.z, a.ingress, a.pass, a.stats);
   }
 }
 

@@ -23,6 +23,8 @@ int xsknf_gpu_lb_host(uint8_t *umem, uint64_t umem_size, const struct xsknf_gpu_
   if (n && (!umem || !descs || !verdicts)) return -EINVAL;
   uint64_t st[lb::kStats] = {0};
   const lb::Tables t = {lb->svc, lb->bk, lb->keys, lb->vals, &lb->count, lb->svc_slots, lb->slots, lb->max_sessions};
+  const lb::Gate none = {nullptr, nullptr, 0};
+  const int32_t pass = lb::pass_verdict(ingress_ifindex, num_interfaces);
   st[lb::kFrames] = n;
   for (uint32_t i = 0; i < n; ++i) {
     const uint64_t off = desc_offset(descs[i].addr);
@@ -32,7 +34,7 @@ int xsknf_gpu_lb_host(uint8_t *umem, uint64_t umem_size, const struct xsknf_gpu_
       ++st[lb::kDropped];
       continue;
     }
-    verdicts[i] = lb::frame(t, umem + off, len, ingress_ifindex, num_interfaces, st);
+    verdicts[i] = lb::frame(t, none, umem + off, len, ingress_ifindex, pass, st);
   }
   if (stats)
     for (int k = 0; k < lb::kStats; ++k) stats[k] = st[k];

@@ -193,6 +193,11 @@ enum Parse : int { kDrop = 0, kPass = 1, kCandidate = 2 };
 XSKNF_HD inline int32_t pass_verdict(uint32_t ingress, uint32_t nif) {
   return nif > 1 ? static_cast<int32_t>((ingress + 1) % nif) : -1;
 }
+// The lbfw NF's PASS (examples/lbfw/lbfw_user.c:435, 476, 518): no -1 for one
+// interface.  nif != 0 is the caller's to refuse.
+XSKNF_HD inline int32_t lbfw_pass_verdict(uint32_t ingress, uint32_t nif) {
+  return static_cast<int32_t>((ingress + 1) % nif);
+}
 // load_balancer_user.c:398-446 on bytes; for a candidate `next` and `proto` are set.
 XSKNF_HD inline Parse parse(const uint8_t *f, uint32_t len, uint32_t &next, uint32_t &proto) {
   if (len < 14) return kDrop;
@@ -235,13 +240,25 @@ XSKNF_HD inline int32_t rewrite(uint8_t *f, uint32_t next, uint32_t proto, const
 }
 
 // stats words (XSKNF_GPU_LB_STATS)
-enum Stat : int { kFrames, kRewritten, kPassed, kDropped, kCreated, kFailed, kOrdered, kReserved, kStats };
+enum Stat : int { kFrames, kRewritten, kPassed, kDropped, kCreated, kFailed, kOrdered, kGated, kStats };
 
-// One frame of the reference's loop (load_balancer_user.c:396-553) against the
-// tables, the inserts included; counts everything but kFrames and kOrdered.
+// The lbfw NF's gate (rule 6a): an ACL table (acl_table.h) on the host or the
+// device.  keys == nullptr: no gate -- the load balancer, and lbfw with
+// acl == NULL.
+struct Gate {
+  const AclKey *keys;
+  const int32_t *actions;
+  uint32_t slots;
+};
+
+// One frame of the reference's loop against the tables, the inserts included;
+// counts everything but kFrames and kOrdered.  One body for both NFs: the load
+// balancer (load_balancer_user.c:396-553) gives its PASS and no gate, lbfw
+// (examples/lbfw/lbfw_user.c:420-594) its own PASS and the ACL.  `pass` is the
+// batch's PASS verdict, computed once by the caller.
 template <typename Counter>
-XSKNF_HD inline int32_t frame(const Tables &t, uint8_t *f, uint32_t len, uint32_t ingress, uint32_t nif,
-                              Counter *stats) {
+XSKNF_HD inline int32_t frame(const Tables &t, const Gate &gate, uint8_t *f, uint32_t len, uint32_t ingress,
+                              int32_t pass, Counter *stats) {
   uint32_t next = 0, proto = 0;
   const Parse p = parse(f, len, next, proto);
   if (p == kDrop) {
@@ -250,9 +267,16 @@ XSKNF_HD inline int32_t frame(const Tables &t, uint8_t *f, uint32_t len, uint32_
   }
   if (p == kPass) {
     ++stats[kPassed];
-    return pass_verdict(ingress, nif);
+    return pass;
   }
   const Key sid = session_key(f, next, proto);
+  if (gate.keys) {   // rule 6a: the rule's action, 0 included; no byte and no session touched
+    const uint32_t g = acl_find(gate.keys, gate.slots, sid.a, sid.b, sid.c, sid.p);
+    if (g != kAclNone) {
+      ++stats[kGated];
+      return gate.actions[g];
+    }
+  }
   Val rep;
   const uint32_t s = find(t.keys, t.slots, sid);
   if (s != kNone) {
@@ -261,7 +285,7 @@ XSKNF_HD inline int32_t frame(const Tables &t, uint8_t *f, uint32_t len, uint32_
     const Service *svc = find_service(t.svc, t.svc_slots, sid.b, (sid.c >> 16) | proto << 16);
     if (!svc) {
       ++stats[kPassed];
-      return pass_verdict(ingress, nif);
+      return pass;
     }
     const Backend b = t.bk[backend_of(*svc, sid)];
     rep = forward_val(b);
