@@ -28,6 +28,13 @@
 
 namespace {
 
+// Two fields of kernel_lb.h are sized by limits that include/xsknf_gpu.h sets:
+// state[f] keeps a HIT's session slot in its low 24 bits (st & 0xffffff), and a
+// staging word is enc(frame, kind) = (frame + 1) << 1 | kind in 32 bits.
+static_assert(XSKNF_GPU_LB_MAX_SLOTS - 1 <= 0xffffffu, "a session slot must fit state[f]'s 24-bit slot field");
+static_assert(((static_cast<uint64_t>(XSKNF_GPU_LB_MAX_BATCH - 1) + 1) << 1 | 1) <= 0xffffffffull,
+              "enc(XSKNF_GPU_LB_MAX_BATCH - 1, 1) must fit a 32-bit staging word");
+
 uint32_t stage_slots(uint32_t n) {
   uint32_t s = 64;
   while (s < 4ull * n) s *= 2;
