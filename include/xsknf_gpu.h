@@ -947,6 +947,79 @@ XSKNF_GPU_API int xsknf_gpu_lbfw_host(uint8_t *umem, uint64_t umem_size, const s
 		uint32_t n, uint32_t ingress_ifindex, uint32_t num_interfaces, const struct xsknf_gpu_acl *acl /* may be NULL */,
 		struct xsknf_gpu_lb *lb, int32_t *verdicts, uint64_t *stats);
 
+/* ---- the macswap NF: every frame's two MAC addresses exchanged in place ------
+ * The reference's examples/macswap with the per-frame callback
+ * (macswap_user.c:34-50, macswap.h:6-36): exchange the destination and the
+ * source MAC address and send the frame back out.  It is the NF the reference's
+ * "pure I/O" figures are taken with; here it is the batch path with next to
+ * nothing to do per frame.  These calls do it for a whole batch, on the device
+ * or (the model the device is held to) on one CPU thread.  The verdicts are
+ * what xsknf_gpu_route_batch consumes.
+ *
+ * Per frame, with f and len as for the firewall (rule 0 gives off):
+ *   0. not (off <= umem_size && len <= umem_size - off)   -> -1, no byte read or written
+ *   1. len < 14                                           -> -1, the frame untouched
+ *                                                            whatever the action
+ *   2. f[0..5] and f[6..11] are exchanged; with double_macswap != 0 they are
+ *      exchanged twice (swap_mac_addresses, then swap_mac_addresses_v2), so
+ *      every byte is as it was
+ *   3. action DROP                                        -> -1
+ *      action REDIRECT and action PASS                    -> (int32_t)((ingress_ifindex + 1u)
+ *                                                            % num_interfaces)
+ *      in 32-bit unsigned arithmetic: ingress 0xFFFFFFFF gives 0.
+ * A quirk kept: on the AF_XDP path the reference's PASS is a REDIRECT (line 48
+ * tests for DROP alone; only its XDP program hands a PASS frame to the stack).
+ *
+ * Deviations from the reference: rule 0 (the kernel's rx validation never shows
+ * the reference such a descriptor); num_interfaces == 0 with an action other
+ * than DROP, where the reference divides by zero, is -EINVAL; with
+ * double_macswap the device call may leave the frame unread and unwritten (the
+ * reference does the work twice so as to time it; the bytes come out the same).
+ *
+ * The descriptors of a batch address disjoint byte ranges, which AF_XDP
+ * guarantees; overlapping frames are undefined.
+ *
+ * The store contract.  The only bytes stored are [off, off + 12) of the frames
+ * that pass rules 0 and 1, and verdicts[0 .. n).  No store covers a byte
+ * outside them, not even with the value that was read there: two 14-byte frames
+ * packed back to back at an odd offset share an aligned 4-byte word, and a lane
+ * that rewrote the whole word would race with its neighbour's.  The device
+ * stores the aligned 4-byte words that lie wholly inside the 12 bytes as words
+ * and the edges as bytes and aligned 2-byte halves.  Frame bytes are READ as the
+ * aligned 4-byte words that hold a byte of [off, off + 12), so up to 3 bytes
+ * around them are read with them (see xsknf_gpu_firewall_batch). */
+#define XSKNF_MACSWAP_ACTION_REDIRECT 0   /* enum action, examples/macswap/macswap_user.c:18-22 */
+#define XSKNF_MACSWAP_ACTION_DROP 1
+#define XSKNF_MACSWAP_ACTION_PASS 2
+
+/* The globals the reference callback reads (macswap_user.c:28-29, :32). */
+struct xsknf_macswap_opts {
+	uint32_t action;           /* opt_action (-c REDIRECT|DROP|PASS), default REDIRECT */
+	uint32_t double_macswap;   /* opt_double_macswap (-d): 0, or anything else for twice */
+	uint32_t num_interfaces;   /* config.num_interfaces (must be >= 1 unless action is DROP) */
+	uint32_t reserved;         /* must be 0 */
+};
+
+/* One batch on the current device, asynchronously on `stream` (a hipStream_t;
+ * NULL: the default stream).  umem (16-byte aligned), descs (16-byte aligned)
+ * and verdicts (4-byte aligned) are device memory; opts is host memory, read at
+ * the call: it may be changed as soon as the call returns.  Written: what the
+ * store contract above names, nothing else.  n == 0 succeeds without a launch.
+ * -EINVAL, before any GPU call: a NULL opts, an action above 2, a nonzero
+ * reserved, num_interfaces == 0 with an action other than DROP (the validation
+ * of xsknf_gpu_checksum_batch: the same callback line); a misaligned umem,
+ * descs or verdicts; with n > 0 a NULL umem, descs or verdicts.  -EIO on a HIP
+ * error, with xsknf_gpu_last_error() set. */
+XSKNF_GPU_API int xsknf_gpu_macswap_batch(uint8_t *umem, uint64_t umem_size, const struct xsknf_gpu_desc *descs,
+		uint32_t n, uint32_t ingress_ifindex, const struct xsknf_macswap_opts *opts, int32_t *verdicts,
+		void *stream);
+/* The same on host arrays: one thread, byte reads and writes only (both
+ * exchanges of a double swap are carried out), no GPU call and no alignment
+ * asked.  -EINVAL for the opts as above and, with n > 0, a NULL umem, descs or
+ * verdicts. */
+XSKNF_GPU_API int xsknf_gpu_macswap_host(uint8_t *umem, uint64_t umem_size, const struct xsknf_gpu_desc *descs,
+		uint32_t n, uint32_t ingress_ifindex, const struct xsknf_macswap_opts *opts, int32_t *verdicts);
+
 /* Text of the last HIP error seen by this library, on any thread (a copy
  * private to the calling thread). */
 XSKNF_GPU_API const char *xsknf_gpu_last_error(void);

@@ -73,6 +73,8 @@ EXPORTED_SYMBOLS = (
     "xsknf_gpu_lb_host",
     "xsknf_gpu_lbfw_batch",
     "xsknf_gpu_lbfw_host",
+    "xsknf_gpu_macswap_batch",
+    "xsknf_gpu_macswap_host",
 )
 
 LB_MAX_SERVICES = 1024      # XSKNF_GPU_LB_MAX_SERVICES
@@ -97,6 +99,10 @@ PATH_RESIDENT = 2
 ACTION_REDIRECT = 0
 ACTION_DROP = 1
 
+MACSWAP_ACTION_REDIRECT = 0   # XSKNF_MACSWAP_ACTION_*
+MACSWAP_ACTION_DROP = 1
+MACSWAP_ACTION_PASS = 2
+
 
 class CsumOpts(ctypes.Structure):
     """struct xsknf_csum_opts (include/xsknf_gpu.h)."""
@@ -107,6 +113,13 @@ class CsumOpts(ctypes.Structure):
         ("num_interfaces", ctypes.c_uint32),
         ("reserved", ctypes.c_uint32),
     ]
+
+
+class MacswapOpts(ctypes.Structure):
+    """struct xsknf_macswap_opts (include/xsknf_gpu.h)."""
+
+    _fields_ = [("action", ctypes.c_uint32), ("double_macswap", ctypes.c_uint32), ("num_interfaces", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
 
 
 class LaunchCfg(ctypes.Structure):
@@ -342,6 +355,11 @@ def load() -> ctypes.CDLL:
     lib.xsknf_gpu_lbfw_batch.argtypes = [vp, u64, vp, u32, u32, u32, vp, vp, vp, vp, u64, vp, vp]
     lib.xsknf_gpu_lbfw_host.restype = ctypes.c_int
     lib.xsknf_gpu_lbfw_host.argtypes = [vp, u64, vp, u32, u32, u32, vp, vp, vp, vp]
+    # the macswap NF
+    lib.xsknf_gpu_macswap_batch.restype = ctypes.c_int
+    lib.xsknf_gpu_macswap_batch.argtypes = [vp, u64, vp, u32, u32, ctypes.POINTER(MacswapOpts), vp, vp]
+    lib.xsknf_gpu_macswap_host.restype = ctypes.c_int
+    lib.xsknf_gpu_macswap_host.argtypes = [vp, u64, vp, u32, u32, ctypes.POINTER(MacswapOpts), vp]
     lib.xsknf_gpu_pool_guard_trips.restype = ctypes.c_int
     lib.xsknf_gpu_pool_guard_trips.argtypes = [ctypes.POINTER(ctypes.c_uint32), ctypes.c_int]
     _lib = lib
