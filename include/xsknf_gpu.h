@@ -667,8 +667,8 @@ struct xsknf_gpu_acl;        /* opaque */
 struct xsknf_gpu_acl_info {
 	uint32_t rules;          /* distinct keys in the table */
 	uint32_t slots;          /* key slots (a power of two > rules) */
-	uint32_t max_probe;      /* slots looked at for the worst-placed rule (0 for an empty ACL) */
-	uint32_t reserved;
+	uint32_t max_probe;      /* slots looked at for the worst-placed rule (0 for an empty ACL), kept across updates */
+	uint32_t tombstones;     /* slots that mark a deleted key (xsknf_gpu_acl_update); 0 after _create */
 	uint64_t device_bytes;   /* 20 * slots (0: built where no device was visible) */
 };
 
@@ -706,9 +706,71 @@ XSKNF_GPU_API int xsknf_gpu_acl_parse(const char *path, struct xsknf_gpu_acl_rul
 XSKNF_GPU_API int xsknf_gpu_acl_create(struct xsknf_gpu_acl **acl_out, const struct xsknf_gpu_acl_rule *rules,
 		uint32_t n, uint32_t slots);
 XSKNF_GPU_API int xsknf_gpu_acl_info(const struct xsknf_gpu_acl *acl, struct xsknf_gpu_acl_info *info);
-/* Free the table on the device and the host (no batch that uses it may be in
- * flight).  -EINVAL for NULL. */
+/* Free the table on the device and the host, and the updates' buffers (no
+ * batch that uses it and no update may be in flight).  -EINVAL for NULL. */
 XSKNF_GPU_API int xsknf_gpu_acl_destroy(struct xsknf_gpu_acl *acl);
+
+/* Change the rules of a live ACL: n ops applied in index order to the
+ * exact-match map.  PUT stores the rule's key with its action or replaces the
+ * key's action; DELETE removes the key (its action is ignored; an absent key is
+ * no error); the last op on a key wins.  A PUT whose proto is neither 6 nor 17
+ * is left out, as _create leaves such a rule out, and a DELETE of such a key
+ * does nothing.
+ *
+ * Everything is validated before anything changes.  -EINVAL: a NULL acl, a NULL
+ * ops with n > 0, an op other than 0 and 1.  -ENOSPC: the map after all ops
+ * would hold `slots` or more distinct keys, or more than
+ * XSKNF_GPU_ACL_MAX_RULES; the slot count never changes (a larger table is
+ * _create's).  -ENOMEM.  In all these cases neither table is touched.  n == 0
+ * succeeds and launches nothing.
+ *
+ * The host table is updated before the call returns: xsknf_gpu_firewall_host
+ * and xsknf_gpu_lbfw_host see the new rules at once.  The device table, on the
+ * current device (the one the ACL was created on), is updated asynchronously
+ * on `stream` (a hipStream_t; NULL: the default stream): a batch enqueued on
+ * that stream before the call sees the old rules, one enqueued after it the new
+ * ones, and the host waits for nothing in between.  ops is not referenced
+ * after the call returns: what the stream needs is copied into pinned buffers
+ * that belong to the ACL, one per update in flight, reused once the stream has
+ * passed them and released by _destroy.  A batch that reads this ACL on another
+ * stream must be ordered against the update by the caller, with an event;
+ * lookups that run beside an update are undefined (a slot's 16-byte key and its
+ * 4-byte action are two stores).  -EIO on a HIP error (xsknf_gpu_last_error()):
+ * the host table holds the new rules and the device table may not; destroy it.
+ *
+ * Once the stream has passed the update the device table equals the host table
+ * byte for byte, keys and actions, in every slot; both are a deterministic
+ * function of _create's arguments and the sequence of update calls.  An object
+ * built in a process with no device visible updates its host table alone and
+ * ignores `stream`.
+ *
+ * How (xsknf_amd/csrc/acl_table.h, acl.cpp): a deleted key's slot becomes the
+ * tombstone {0, 0, 0, 0xffffffff}, which a probe walks over and no frame's key
+ * equals; a new key takes the first tombstone of its probe sequence.  The
+ * device receives one 24-byte record {slot, key, action} per changed slot and
+ * scatters them (acl_update_device.hip).  When more than a quarter of the slots
+ * would be tombstones, or no slot would stay empty, the call rebuilds the host
+ * table in place (the live rules reinserted in ascending slot order, no
+ * tombstone left) and sends the whole table instead. */
+#define XSKNF_GPU_ACL_PUT 0u
+#define XSKNF_GPU_ACL_DELETE 1u
+struct xsknf_gpu_acl_op {
+	struct xsknf_gpu_acl_rule rule;
+	uint32_t op;             /* XSKNF_GPU_ACL_PUT or _DELETE */
+};                           /* 24 bytes */
+XSKNF_GPU_API int xsknf_gpu_acl_update(struct xsknf_gpu_acl *acl, const struct xsknf_gpu_acl_op *ops, uint32_t n,
+		void *stream);
+/* Every live rule of the host table (which == XSKNF_GPU_ACL_HOST_TABLE) or the
+ * device table (_DEVICE_TABLE; waits for the device), ascending by {saddr, daddr,
+ * sport | dport << 16, proto} compared as numbers in that order, pad 0.  *n_out
+ * is the table's count; at most cap rules are written (-ENOSPC if cap is
+ * smaller; rules_out may be NULL with cap 0).  For tests and monitoring.
+ * -EINVAL for a NULL acl or n_out or another `which`; -ENODEV for the device
+ * table of a host-only object. */
+#define XSKNF_GPU_ACL_HOST_TABLE 0
+#define XSKNF_GPU_ACL_DEVICE_TABLE 1
+XSKNF_GPU_API int xsknf_gpu_acl_dump(const struct xsknf_gpu_acl *acl, int which, struct xsknf_gpu_acl_rule *rules_out,
+		uint32_t cap, uint32_t *n_out);
 
 /* verdicts[i] = the firewall's verdict for descs[i], i < n, on the current
  * device (the one the ACL was created on), asynchronously on `stream` (a

@@ -8,7 +8,7 @@ from .checksummer import (ACTION_DROP, ACTION_REDIRECT, Checksummer, Checksummer
                           parse_command_line)
 from .lb import LB_STATS, LoadBalancer
 from .lbfw import LBFW_STATS
-from ._lib import MACSWAP_ACTION_DROP, MACSWAP_ACTION_PASS, MACSWAP_ACTION_REDIRECT
+from ._lib import ACL_DELETE, ACL_PUT, MACSWAP_ACTION_DROP, MACSWAP_ACTION_PASS, MACSWAP_ACTION_REDIRECT
 from .macswap import macswap_batch, macswap_host
 # The library options (src/xsknf.c:777-874) are parsed by the runtime's C
 # xsknf_parse_args since round 2; these names keep the round-1 Python API
@@ -16,7 +16,7 @@ from .macswap import macswap_batch, macswap_host
 from .runtime import Config as XsknfConfig
 from .runtime import parse_args
 
-__all__ = ["ACTION_DROP", "ACTION_REDIRECT", "Checksummer", "ChecksummerOptions", "HostPath", "LB_STATS", "LBFW_STATS", "LoadBalancer",
+__all__ = ["ACL_DELETE", "ACL_PUT", "ACTION_DROP", "ACTION_REDIRECT", "Checksummer", "ChecksummerOptions", "HostPath", "LB_STATS", "LBFW_STATS", "LoadBalancer",
            "MACSWAP_ACTION_DROP", "MACSWAP_ACTION_PASS", "MACSWAP_ACTION_REDIRECT", "XsknfConfig", "macswap_batch",
            "macswap_host", "parse_args", "parse_command_line"]
 __version__ = "0.1.0"

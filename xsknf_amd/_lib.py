@@ -61,6 +61,8 @@ EXPORTED_SYMBOLS = (
     "xsknf_gpu_acl_create",
     "xsknf_gpu_acl_info",
     "xsknf_gpu_acl_destroy",
+    "xsknf_gpu_acl_update",
+    "xsknf_gpu_acl_dump",
     "xsknf_gpu_firewall_batch",
     "xsknf_gpu_firewall_host",
     "xsknf_gpu_lb_create",
@@ -86,6 +88,10 @@ LB_STATS = 8                # XSKNF_GPU_LB_STATS
 
 ACL_MAX_RULES = 1000000     # XSKNF_GPU_ACL_MAX_RULES
 ACL_MAX_SLOTS = 1 << 24     # XSKNF_GPU_ACL_MAX_SLOTS
+ACL_PUT = 0                 # XSKNF_GPU_ACL_PUT, the op of struct xsknf_gpu_acl_op
+ACL_DELETE = 1
+ACL_HOST_TABLE = 0          # xsknf_gpu_acl_dump's `which`
+ACL_DEVICE_TABLE = 1
 
 ROUTE_MAX_INTERFACES = 32   # XSKNF_GPU_ROUTE_MAX_INTERFACES
 FORWARD_STATS = 3           # XSKNF_GPU_FORWARD_STATS
@@ -164,7 +170,7 @@ class AclInfo(ctypes.Structure):
     """struct xsknf_gpu_acl_info (include/xsknf_gpu.h)."""
 
     _fields_ = [("rules", ctypes.c_uint32), ("slots", ctypes.c_uint32), ("max_probe", ctypes.c_uint32),
-                ("reserved", ctypes.c_uint32), ("device_bytes", ctypes.c_uint64)]
+                ("tombstones", ctypes.c_uint32), ("device_bytes", ctypes.c_uint64)]
 
 
 class LbInfo(ctypes.Structure):
@@ -329,6 +335,10 @@ def load() -> ctypes.CDLL:
     lib.xsknf_gpu_acl_info.argtypes = [vp, ctypes.POINTER(AclInfo)]
     lib.xsknf_gpu_acl_destroy.restype = ctypes.c_int
     lib.xsknf_gpu_acl_destroy.argtypes = [vp]
+    lib.xsknf_gpu_acl_update.restype = ctypes.c_int
+    lib.xsknf_gpu_acl_update.argtypes = [vp, vp, ctypes.c_uint32, vp]
+    lib.xsknf_gpu_acl_dump.restype = ctypes.c_int
+    lib.xsknf_gpu_acl_dump.argtypes = [vp, ctypes.c_int, vp, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
     lib.xsknf_gpu_firewall_batch.restype = ctypes.c_int
     lib.xsknf_gpu_firewall_batch.argtypes = [vp, u64, vp, ctypes.c_uint32, vp, vp, vp]
     lib.xsknf_gpu_firewall_host.restype = ctypes.c_int

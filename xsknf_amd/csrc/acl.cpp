@@ -1,9 +1,12 @@
 // acl.cpp -- the firewall's ACL (include/xsknf_gpu.h xsknf_gpu_acl_*): the
 // reference's rule file read (init_acl, examples/firewall/firewall_user.c:53-116)
 // and the rules built into the open-addressing table of acl_table.h on one host
-// thread.  Plain C++; the only GPU calls are the table's allocation, upload and
-// release, and a build with XSKNF_ACL_HOST_ONLY has none (the sanitizer program,
-// tests/c/san_firewall.c, links this file and firewall_host.cpp alone).
+// thread, and the updates of a live table (xsknf_gpu_acl_update: tombstones, the
+// rebuild in place, the dirty slots as records for acl_update_device.hip).
+// Plain C++; the only GPU calls are the table's allocation, upload, read-back
+// (_dump) and release, and a build with XSKNF_ACL_HOST_ONLY has none (the
+// sanitizer programs, tests/c/san_firewall.c and san_acl_update.c, link this
+// file and firewall_host.cpp alone).
 #include <arpa/inet.h>
 #include <errno.h>
 #include <stdint.h>
@@ -11,8 +14,10 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <new>
 #include <string>
+#include <vector>
 
 #include "acl_table.h"
 
@@ -70,7 +75,106 @@ bool parse_addr(const char *tok, size_t len, uint32_t &out) {
 void free_acl(xsknf_gpu_acl *acl) {
   free(acl->keys);
   free(acl->actions);
+  free(acl->probe_hist);
   delete acl;
+}
+
+// ---- updates ------------------------------------------------------------------
+
+using xsknf_gpu::kAclNone;
+using xsknf_gpu::kAclTombstoneP;
+
+constexpr AclKey kTombstone = {0, 0, 0, kAclTombstoneP};
+
+inline AclKey key_of(const struct xsknf_gpu_acl_rule &r) {
+  return AclKey{r.saddr, r.daddr, static_cast<uint32_t>(r.sport) | static_cast<uint32_t>(r.dport) << 16, r.proto};
+}
+inline bool same(const AclKey &x, const AclKey &y) { return x.a == y.a && x.b == y.b && x.c == y.c && x.p == y.p; }
+inline bool live(const AclKey &k) { return k.p != 0 && k.p != kAclTombstoneP; }
+
+// Where key k is, or where it would go: the probe runs to the key or to an
+// empty slot (one always remains) and remembers the first tombstone on its way.
+struct Place {
+  bool found;
+  uint32_t slot, probes;   // the key's slot, or the first tombstone's, or else the empty slot's
+};
+Place place_of(const xsknf_gpu_acl *acl, const AclKey &k) {
+  const uint32_t mask = acl->slots - 1;
+  uint32_t s = xsknf_gpu::acl_hash(k.a, k.b, k.c, k.p) & mask, tomb = kAclNone, tomb_probes = 0;
+  for (uint32_t probes = 1;; ++probes, s = (s + 1) & mask) {
+    const AclKey &e = acl->keys[s];
+    if (e.p == 0) return tomb != kAclNone ? Place{false, tomb, tomb_probes} : Place{false, s, probes};
+    if (e.p == kAclTombstoneP) {
+      if (tomb == kAclNone) {
+        tomb = s;
+        tomb_probes = probes;
+      }
+    } else if (same(e, k)) {
+      return Place{true, s, probes};
+    }
+  }
+}
+
+// The same slot count, the live rules reinserted in ascending slot order of the
+// old table, no tombstone left.  live_k / live_a: room for acl->rules entries.
+void rebuild_in_place(xsknf_gpu_acl *acl, AclKey *live_k, int32_t *live_a) {
+  uint32_t n = 0;
+  for (uint32_t s = 0; s < acl->slots; ++s)
+    if (live(acl->keys[s])) {
+      live_k[n] = acl->keys[s];
+      live_a[n++] = acl->actions[s];
+    }
+  memset(acl->keys, 0, sizeof(AclKey) * acl->slots);
+  memset(acl->actions, 0, sizeof(int32_t) * acl->slots);
+  memset(acl->probe_hist, 0, sizeof(uint32_t) * (static_cast<size_t>(acl->max_probe) + 1));
+  acl->max_probe = 0;
+  acl->tombstones = 0;
+  const uint32_t mask = acl->slots - 1;
+  for (uint32_t i = 0; i < n; ++i) {
+    const AclKey &k = live_k[i];
+    uint32_t s = xsknf_gpu::acl_hash(k.a, k.b, k.c, k.p) & mask, probes = 1;
+    while (acl->keys[s].p) {   // (the keys are distinct and fewer than the slots)
+      s = (s + 1) & mask;
+      ++probes;
+    }
+    acl->keys[s] = k;
+    acl->actions[s] = live_a[i];
+    ++acl->probe_hist[probes];
+    if (probes > acl->max_probe) acl->max_probe = probes;
+  }
+}
+
+// the live rules of a table, ascending by key
+int dump_table(const AclKey *keys, const int32_t *actions, uint32_t slots, struct xsknf_gpu_acl_rule *out, uint32_t cap,
+               uint32_t *n_out) {
+  std::vector<uint32_t> used;
+  try {
+    for (uint32_t s = 0; s < slots; ++s)
+      if (live(keys[s])) used.push_back(s);
+  } catch (const std::bad_alloc &) {
+    return -ENOMEM;
+  }
+  std::sort(used.begin(), used.end(), [keys](uint32_t x, uint32_t y) {
+    const AclKey &a = keys[x], &b = keys[y];
+    if (a.a != b.a) return a.a < b.a;
+    if (a.b != b.b) return a.b < b.b;
+    if (a.c != b.c) return a.c < b.c;
+    return a.p < b.p;
+  });
+  *n_out = static_cast<uint32_t>(used.size());
+  for (uint32_t i = 0; i < used.size() && i < cap; ++i) {
+    const AclKey &k = keys[used[i]];
+    struct xsknf_gpu_acl_rule r;
+    memset(&r, 0, sizeof(r));
+    r.saddr = k.a;
+    r.daddr = k.b;
+    r.sport = static_cast<uint16_t>(k.c);
+    r.dport = static_cast<uint16_t>(k.c >> 16);
+    r.proto = static_cast<uint8_t>(k.p);
+    r.action = actions[used[i]];
+    out[i] = r;
+  }
+  return used.size() > cap ? -ENOSPC : 0;
 }
 
 }  // namespace
@@ -143,7 +247,8 @@ int xsknf_gpu_acl_create(struct xsknf_gpu_acl **acl_out, const struct xsknf_gpu_
   acl->slots = slots;
   acl->keys = static_cast<AclKey *>(calloc(slots, sizeof(AclKey)));
   acl->actions = static_cast<int32_t *>(calloc(slots, sizeof(int32_t)));
-  if (!acl->keys || !acl->actions) {
+  acl->probe_hist = static_cast<uint32_t *>(calloc(static_cast<size_t>(slots) + 1, sizeof(uint32_t)));
+  if (!acl->keys || !acl->actions || !acl->probe_hist) {
     free_acl(acl);
     return -ENOMEM;
   }
@@ -166,6 +271,7 @@ int xsknf_gpu_acl_create(struct xsknf_gpu_acl **acl_out, const struct xsknf_gpu_
       }
       acl->keys[s] = k;
       ++acl->rules;
+      ++acl->probe_hist[probes];
       if (probes > acl->max_probe) acl->max_probe = probes;
     }
     acl->actions[s] = r.action;   // the last rule of a key wins
@@ -202,7 +308,7 @@ int xsknf_gpu_acl_info(const struct xsknf_gpu_acl *acl, struct xsknf_gpu_acl_inf
   info->rules = acl->rules;
   info->slots = acl->slots;
   info->max_probe = acl->max_probe;
-  info->reserved = 0;
+  info->tombstones = acl->tombstones;
   info->device_bytes = acl->d_keys ? (sizeof(AclKey) + sizeof(int32_t)) * static_cast<uint64_t>(acl->slots) : 0;
   return 0;
 }
@@ -212,6 +318,7 @@ int xsknf_gpu_acl_destroy(struct xsknf_gpu_acl *acl) {
   int rc = 0;
 #ifndef XSKNF_ACL_HOST_ONLY
   if (acl->d_keys) {
+    rc = xsknf_gpu::acl_staging_release(acl);
     const hipError_t e = hipFree(acl->d_keys);
     if (e != hipSuccess) {
       xsknf_gpu::set_error(e, "ACL release");
@@ -221,6 +328,159 @@ int xsknf_gpu_acl_destroy(struct xsknf_gpu_acl *acl) {
 #endif
   free_acl(acl);
   return rc;
+}
+
+int xsknf_gpu_acl_update(struct xsknf_gpu_acl *acl, const struct xsknf_gpu_acl_op *ops, uint32_t n, void *stream) {
+  if (!acl || (n && !ops)) return -EINVAL;
+  for (uint32_t i = 0; i < n; ++i)
+    if (ops[i].op != XSKNF_GPU_ACL_PUT && ops[i].op != XSKNF_GPU_ACL_DELETE) return -EINVAL;
+  if (n == 0) return 0;
+  const uint32_t slots = acl->slots, mask = slots - 1;
+
+  // Pass 1, nothing changed yet.  The last op of a key stands for the key: the
+  // ops are walked backwards and a key seen before (in a scratch table of op
+  // indices) is skipped.  What is left splits into the slots to delete and the
+  // puts; both are applied in ascending op order, the deletes first, so the
+  // table never holds more keys than before or after the call.
+  std::vector<uint32_t> seen, dels, puts, dirty;
+  uint32_t n_new = 0;
+  AclKey *live_k = nullptr;
+  int32_t *live_a = nullptr;
+  bool rebuild = false;
+  try {
+    size_t cap = 16;
+    while (cap < 2 * static_cast<size_t>(n)) cap *= 2;
+    seen.assign(cap, kAclNone);
+    for (uint32_t i = n; i-- > 0;) {
+      const struct xsknf_gpu_acl_rule &r = ops[i].rule;
+      if (r.proto != 6 && r.proto != 17) continue;   // rule 5: never in the table
+      const AclKey k = key_of(r);
+      size_t s = xsknf_gpu::acl_hash(k.a, k.b, k.c, k.p) & (cap - 1);
+      while (seen[s] != kAclNone && !same(key_of(ops[seen[s]].rule), k)) s = (s + 1) & (cap - 1);
+      if (seen[s] != kAclNone) continue;
+      seen[s] = i;
+      const uint32_t at = xsknf_gpu::acl_find(acl->keys, slots, k.a, k.b, k.c, k.p);
+      if (ops[i].op == XSKNF_GPU_ACL_DELETE) {
+        if (at != kAclNone) dels.push_back(at);
+      } else {
+        puts.push_back(i);
+        n_new += at == kAclNone;
+      }
+    }
+    std::vector<uint32_t>().swap(seen);
+    std::reverse(dels.begin(), dels.end());
+    std::reverse(puts.begin(), puts.end());
+    const uint64_t after = static_cast<uint64_t>(acl->rules) - dels.size() + n_new;
+    if (after >= slots || after > XSKNF_GPU_ACL_MAX_RULES) return -ENOSPC;
+    if (dels.empty() && puts.empty()) return 0;
+    // the bound of acl_table.h, taken where the deletes are in and the puts are not
+    const uint64_t tombs = static_cast<uint64_t>(acl->tombstones) + dels.size();
+    rebuild = tombs > slots / xsknf_gpu::kAclTombstoneShare || after + tombs > slots - 1;
+    if (rebuild) {
+      const size_t keep = acl->rules - dels.size();
+      live_k = static_cast<AclKey *>(malloc(sizeof(AclKey) * (keep ? keep : 1)));
+      live_a = static_cast<int32_t *>(malloc(sizeof(int32_t) * (keep ? keep : 1)));
+      if (!live_k || !live_a) throw std::bad_alloc();
+    } else {
+      dirty.reserve(dels.size() + puts.size());
+    }
+  } catch (const std::bad_alloc &) {
+    free(live_k);
+    free(live_a);
+    return -ENOMEM;
+  }
+  void *staged = nullptr;
+#ifndef XSKNF_ACL_HOST_ONLY
+  xsknf_gpu::AclStage *stage = nullptr;
+  if (acl->d_keys) {
+    const size_t bytes = rebuild ? (sizeof(AclKey) + sizeof(int32_t)) * static_cast<size_t>(slots)
+                                 : sizeof(xsknf_gpu::AclUpdateRec) * (dels.size() + puts.size());
+    const int rc = xsknf_gpu::acl_stage_acquire(acl, bytes, !rebuild, &stage, &staged);
+    if (rc) {
+      free(live_k);
+      free(live_a);
+      return rc;
+    }
+  }
+#else
+  (void)stream;
+#endif
+
+  // Pass 2: the host table.  Nothing below can fail.
+  for (const uint32_t s : dels) {
+    const AclKey &k = acl->keys[s];
+    const uint32_t probes = ((s - (xsknf_gpu::acl_hash(k.a, k.b, k.c, k.p) & mask)) & mask) + 1;
+    --acl->probe_hist[probes];
+    acl->keys[s] = kTombstone;
+    acl->actions[s] = 0;
+    if (!rebuild) dirty.push_back(s);   // (reserved above)
+  }
+  acl->rules -= static_cast<uint32_t>(dels.size());
+  acl->tombstones += static_cast<uint32_t>(dels.size());
+  while (acl->max_probe && !acl->probe_hist[acl->max_probe]) --acl->max_probe;
+  if (rebuild) {
+    rebuild_in_place(acl, live_k, live_a);
+    free(live_k);
+    free(live_a);
+  }
+  for (const uint32_t i : puts) {
+    const AclKey k = key_of(ops[i].rule);
+    const Place at = place_of(acl, k);
+    if (!at.found) {
+      if (acl->keys[at.slot].p == kAclTombstoneP) --acl->tombstones;
+      acl->keys[at.slot] = k;
+      ++acl->rules;
+      ++acl->probe_hist[at.probes];
+      if (at.probes > acl->max_probe) acl->max_probe = at.probes;
+    }
+    acl->actions[at.slot] = ops[i].rule.action;
+    if (!rebuild) dirty.push_back(at.slot);
+  }
+
+#ifndef XSKNF_ACL_HOST_ONLY
+  // Pass 3: the device table, on the stream.
+  if (!acl->d_keys) return 0;
+  if (rebuild) {
+    memcpy(staged, acl->keys, sizeof(AclKey) * slots);
+    memcpy(static_cast<char *>(staged) + sizeof(AclKey) * slots, acl->actions, sizeof(int32_t) * slots);
+    return xsknf_gpu::acl_enqueue_table(acl, stage, stream);
+  }
+  // a put may have taken a slot this call's delete left: each slot once, as it is now
+  std::sort(dirty.begin(), dirty.end());
+  dirty.erase(std::unique(dirty.begin(), dirty.end()), dirty.end());
+  xsknf_gpu::AclUpdateRec *rec = static_cast<xsknf_gpu::AclUpdateRec *>(staged);
+  for (size_t i = 0; i < dirty.size(); ++i) rec[i] = xsknf_gpu::AclUpdateRec{dirty[i], acl->keys[dirty[i]], acl->actions[dirty[i]]};
+  return xsknf_gpu::acl_enqueue_records(acl, stage, static_cast<uint32_t>(dirty.size()), stream);
+#else
+  (void)staged;
+  return 0;
+#endif
+}
+
+int xsknf_gpu_acl_dump(const struct xsknf_gpu_acl *acl, int which, struct xsknf_gpu_acl_rule *rules_out, uint32_t cap,
+                       uint32_t *n_out) {
+  if (!acl || !n_out || (cap && !rules_out)) return -EINVAL;
+  if (which == XSKNF_GPU_ACL_HOST_TABLE) return dump_table(acl->keys, acl->actions, acl->slots, rules_out, cap, n_out);
+  if (which != XSKNF_GPU_ACL_DEVICE_TABLE) return -EINVAL;
+  if (!acl->d_keys) return -ENODEV;
+#ifndef XSKNF_ACL_HOST_ONLY
+  const size_t kb = sizeof(AclKey) * static_cast<size_t>(acl->slots), ab = sizeof(int32_t) * static_cast<size_t>(acl->slots);
+  char *tmp = static_cast<char *>(malloc(kb + ab));
+  if (!tmp) return -ENOMEM;
+  hipError_t e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(tmp, acl->d_keys, kb + ab, hipMemcpyDeviceToHost);
+  int rc;
+  if (e == hipSuccess) {
+    rc = dump_table(reinterpret_cast<AclKey *>(tmp), reinterpret_cast<int32_t *>(tmp + kb), acl->slots, rules_out, cap, n_out);
+  } else {
+    xsknf_gpu::set_error(e, "ACL dump");
+    rc = -EIO;
+  }
+  free(tmp);
+  return rc;
+#else
+  return -ENODEV;
+#endif
 }
 
 }  // extern "C"

@@ -17,7 +17,19 @@
 // table.  A probe starts at h & (slots - 1) and walks up one slot at a time,
 // wrapping, until the key or an empty slot: at most `slots` steps, and the
 // builder keeps one slot empty.
+//
+// Updates (acl.cpp xsknf_gpu_acl_update) delete a key by overwriting its slot
+// with the tombstone {0, 0, 0, kAclTombstoneP}: its p is not 0, so a probe walks
+// on over it, and it is not 6 or 17, so no frame's key equals it -- acl_lookup,
+// acl_find and the kernels need no word about it.  A new key goes into the first
+// tombstone of its probe sequence, once the probe has reached an empty slot
+// without meeting the key.  The bound: after an update's deletes at most
+// slots / kAclTombstoneShare slots are tombstones, and live keys + tombstones +
+// the update's new keys leave one slot empty; an update that would pass either
+// limit rebuilds the table in place, tombstone-free, before it stores its puts.
+// A probe therefore looks at no more than live keys + tombstones + 1 slots.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #include "desc_rules.h"   // XSKNF_HD
@@ -28,6 +40,21 @@ struct AclKey {
   uint32_t a, b, c, p;
 };
 static_assert(sizeof(AclKey) == 16, "one 16-byte load per probe");
+
+// p of a slot: 0 empty, 6 or 17 a stored key, kAclTombstoneP a deleted one
+constexpr uint32_t kAclTombstoneP = 0xffffffffu;
+constexpr uint32_t kAclTombstoneShare = 4;   // at most slots / 4 tombstones outlive an update's deletes
+
+// One slot's new contents, as an update sends them to the device (acl.cpp
+// writes them, kernel_acl_update.h scatters them).  The records of one update
+// name each slot AT MOST ONCE and carry its final state: the scatter's lanes
+// store without looking at one another.
+struct AclUpdateRec {
+  uint32_t slot;
+  AclKey key;
+  int32_t action;
+};
+static_assert(sizeof(AclUpdateRec) == 24 && alignof(AclUpdateRec) == 4, "three 8-byte loads per record");
 
 XSKNF_HD inline uint32_t acl_hash(uint32_t a, uint32_t b, uint32_t c, uint32_t p) {
   uint32_t h = a * 0x9E3779B1u;
@@ -74,12 +101,34 @@ XSKNF_HD inline uint32_t acl_find(const AclKey *keys, uint32_t slots, uint32_t a
 }  // namespace xsknf_gpu
 
 // The object behind struct xsknf_gpu_acl: the table on the host and, unless
-// built with XSKNF_ACL_HOST_ONLY (the sanitizer program, tests/c/san_firewall.c),
-// its copy on the device current at creation: one allocation, the keys first.
+// built with XSKNF_ACL_HOST_ONLY (the sanitizer programs, tests/c/san_firewall.c
+// and san_acl_update.c), its copy on the device current at creation: one
+// allocation, the keys first.
 struct xsknf_gpu_acl {
   uint32_t slots, rules, max_probe;
   xsknf_gpu::AclKey *keys;     // host, slots entries
   int32_t *actions;            // host, slots entries
   xsknf_gpu::AclKey *d_keys;   // device (NULL in a host-only build)
   int32_t *d_actions;
+  uint32_t tombstones;         // slots that hold the tombstone
+  uint32_t *probe_hist;        // host, slots + 1 entries: [d] = live keys found at their d-th probe (max_probe's source)
+  struct xsknf_gpu_acl_staging *staging;   // acl_update_device.hip: the updates' buffers (NULL until the first one)
 };
+
+#ifndef XSKNF_ACL_HOST_ONLY
+// acl_update_device.hip: how an update reaches the device table.  A stage is a
+// pinned host buffer of at least `bytes` bytes (and, with `records`, a device
+// buffer as large) that no update still in flight uses; acl.cpp fills *host_out
+// and hands the stage to exactly one of the two enqueue calls, after which the
+// stage is busy until `stream` has passed it.  All return 0, -ENOMEM or -EIO
+// (xsknf_gpu_last_error()).
+namespace xsknf_gpu {
+struct AclStage;
+int acl_stage_acquire(xsknf_gpu_acl *acl, size_t bytes, bool records, AclStage **stage_out, void **host_out);
+// n AclUpdateRec at the stage's start: copy them over and scatter them into the table
+int acl_enqueue_records(xsknf_gpu_acl *acl, AclStage *stage, uint32_t n, void *stream);
+// the whole table at the stage's start, keys then actions: copy it over the device table
+int acl_enqueue_table(xsknf_gpu_acl *acl, AclStage *stage, void *stream);
+int acl_staging_release(xsknf_gpu_acl *acl);   // _destroy
+}  // namespace xsknf_gpu
+#endif

@@ -7,7 +7,9 @@ look the 13-byte 5-tuple up in an exact-match ACL and return the rule's action
 rules per frame are in include/xsknf_gpu.h ("the firewall NF").
 
 `Acl` holds the table (xsknf_gpu_acl_*: xsknf_amd/csrc/acl.cpp), on the host and
-on the device that was current when it was made.  `firewall_batch` gives the
+on the device that was current when it was made; `Acl.update` puts, replaces
+and deletes rules of the live table, on the device in stream order
+(xsknf_gpu_acl_update).  `firewall_batch` gives the
 verdicts on the device for a UMEM and descriptors that lie there
 (xsknf_gpu_firewall_batch; xsknf_amd/csrc/firewall_device.hip), `firewall_host`
 on one CPU thread (xsknf_gpu_firewall_host: the model the device is held to).
@@ -30,6 +32,24 @@ MAX_SLOTS = _lib.ACL_MAX_SLOTS
 RULE_DTYPE = np.dtype([("saddr", "<u4"), ("daddr", "<u4"), ("sport", "<u2"), ("dport", "<u2"), ("proto", "u1"),
                        ("pad", "u1", (3,)), ("action", "<i4")])
 assert RULE_DTYPE.itemsize == 20
+# struct xsknf_gpu_acl_op: a rule and what to do with it
+PUT = _lib.ACL_PUT
+DELETE = _lib.ACL_DELETE
+OP_DTYPE = np.dtype([("rule", RULE_DTYPE), ("op", "<u4")])
+assert OP_DTYPE.itemsize == 24
+HOST_TABLE = _lib.ACL_HOST_TABLE
+DEVICE_TABLE = _lib.ACL_DEVICE_TABLE
+
+
+def make_ops(rules, op) -> np.ndarray:
+    """OP_DTYPE records: every rule of `rules` with the same op."""
+    r = np.ascontiguousarray(rules)
+    if r.dtype.itemsize != 20 or r.ndim != 1:
+        raise ValueError("rules must be a 1-d array of 20-byte struct xsknf_gpu_acl_rule records")
+    ops = np.zeros(r.shape[0], dtype=OP_DTYPE)
+    ops["rule"] = r.view(RULE_DTYPE)
+    ops["op"] = op
+    return ops
 
 
 def parse_acl(path) -> np.ndarray:
@@ -88,11 +108,57 @@ class Acl:
 
     @property
     def info(self) -> dict:
-        """rules (distinct keys), slots, max_probe, device_bytes."""
+        """rules (live keys), slots, max_probe, tombstones, device_bytes."""
         i = _lib.AclInfo()
         _lib.check(_lib.load().xsknf_gpu_acl_info(self.handle, ctypes.byref(i)), "xsknf_gpu_acl_info")
         return {"rules": int(i.rules), "slots": int(i.slots), "max_probe": int(i.max_probe),
-                "device_bytes": int(i.device_bytes)}
+                "tombstones": int(i.tombstones), "device_bytes": int(i.device_bytes)}
+
+    def update(self, puts=None, deletes=None, *, ops=None, stream=None) -> None:
+        """xsknf_gpu_acl_update: `deletes` (RULE_DTYPE records whose keys go; the
+        actions are ignored) and then `puts` (rules stored, or whose action
+        replaces the key's), or `ops`, OP_DTYPE records applied in their order.
+        The host table changes before the call returns; the device table on
+        `stream`: a torch stream or a hipStream_t as an int, by default the
+        current torch stream of the current device (the NULL stream for an ACL
+        without a device table).  Only enqueues; a refused update
+        (XsknfGpuError: -ENOSPC, -EINVAL) leaves both tables as they were."""
+        if ops is not None:
+            if puts is not None or deletes is not None:
+                raise ValueError("give puts / deletes or ops, not both")
+            o = np.ascontiguousarray(ops)
+            if o.dtype.itemsize != 24 or o.ndim != 1:
+                raise ValueError("ops must be a 1-d array of 24-byte struct xsknf_gpu_acl_op records")
+        else:
+            parts = [make_ops(deletes, DELETE)] if deletes is not None else []
+            if puts is not None:
+                parts.append(make_ops(puts, PUT))
+            o = np.concatenate(parts) if parts else np.zeros(0, dtype=OP_DTYPE)
+        if stream is None:
+            s = 0
+            if o.size and self.info["device_bytes"]:
+                import torch
+                s = torch.cuda.current_stream().cuda_stream
+        else:
+            s = int(getattr(stream, "cuda_stream", stream))
+        _lib.check(_lib.load().xsknf_gpu_acl_update(self.handle, o.ctypes.data if o.size else None, o.size,
+                                                    ctypes.c_void_p(s or None)), "xsknf_gpu_acl_update")
+
+    def dump(self, device: bool = False) -> np.ndarray:
+        """xsknf_gpu_acl_dump: the live rules of the host table or (waiting for
+        the device) the device table as RULE_DTYPE records, ascending by
+        (saddr, daddr, sport | dport << 16, proto)."""
+        lib = _lib.load()
+        which = DEVICE_TABLE if device else HOST_TABLE
+        n = ctypes.c_uint32(0)
+        rc = lib.xsknf_gpu_acl_dump(self.handle, which, None, 0, ctypes.byref(n))
+        if rc not in (0, -errno.ENOSPC):
+            _lib.check(rc, "xsknf_gpu_acl_dump")
+        rules = np.zeros(int(n.value), dtype=RULE_DTYPE)
+        if rules.size:
+            _lib.check(lib.xsknf_gpu_acl_dump(self.handle, which, rules.ctypes.data, rules.size, ctypes.byref(n)),
+                       "xsknf_gpu_acl_dump")
+        return rules
 
     def close(self) -> None:
         if self._h:
