@@ -937,6 +937,63 @@ XSKNF_GPU_API int xsknf_gpu_lb_sessions_dump(const struct xsknf_gpu_lb *lb, int 
 		struct xsknf_gpu_lb_session_key *keys, struct xsknf_gpu_lb_session_value *values, uint32_t cap,
 		uint32_t *n_out);
 
+/* Removing sessions.  The two session tables are independent, so every call
+ * names one: the plain forms work on the DEVICE table, asynchronously on
+ * `stream`, on the device the object was made on; the _host forms work on the
+ * host table on the calling thread.  A device form reads nothing back and the
+ * host waits for nothing: a batch enqueued on that stream before the call sees
+ * the old table, a batch enqueued after it the new one, and the table's count
+ * drops by what was removed, so a table at max_sessions has room again.  `keys`
+ * is host memory that is not referenced after the call returns.  result (host
+ * forms) / result_dev (device forms: device memory, 8-byte aligned, written on
+ * the stream) is XSKNF_GPU_LB_REMOVE_RESULT uint64 and may be NULL.
+ *
+ * _sessions_remove: set semantics over the table as it stands when the stream
+ * reaches the call.  L = the listed keys that the table holds (duplicates
+ * count once, an absent key is no error, a key whose proto is neither 6 nor 17
+ * matches nothing; pad is ignored).  Without XSKNF_GPU_LB_REMOVE_PAIR exactly L
+ * is removed.  With it the partner of each member of L goes too: for a
+ * TO_BACKEND session {saddr, daddr, sport, dport, p} -> {addr, port} that is the
+ * key {addr, saddr, port, sport, p} (rule 9's backward key), for a TO_CLIENT
+ * one {daddr, addr, dport, port, p} -- but only if the table holds it, its
+ * direction is the opposite one and its own partner is the listed key, so that
+ * an unpaired _sessions_put entry or a backward session that another flow has
+ * replaced takes no stranger with it.  Nothing is transitive.
+ * result[_REMOVED] counts the distinct sessions removed.
+ *
+ * _drain_backend: every TO_BACKEND session whose value is {addr, port} and every
+ * TO_CLIENT session whose key's source is {addr, port}, of protocol proto: both
+ * halves of every flow of that backend.  The backend stays in its service.
+ *
+ * _sessions_clear: every session of one table (`which` as for _sessions_dump;
+ * stream is used for the device table only).
+ *
+ * A removed slot stays a tombstone that lookups walk over and inserts do not
+ * reuse; a removal that leaves more than slots / 4 of them rebuilds the table
+ * free of tombstones (result[_COMPACTED] = 1), on the device without the host
+ * knowing.  The first device removal allocates a spare table of the session
+ * table's size, from then on part of device_bytes.  _sessions_put, _dump and
+ * _info are correct on a table that has seen removals.
+ *
+ * Everything is validated before any work: -EINVAL for a NULL lb, a NULL keys
+ * with n > 0, unknown flag bits, a misaligned result_dev, a proto other than 6
+ * and 17 (_drain_backend) or a bad which.  -ENODEV for a device form on a
+ * host-only object.  -ENOMEM.  -EIO on a HIP error (xsknf_gpu_last_error()).
+ * n == 0 succeeds, launches nothing and writes zeros to a non-NULL result. */
+#define XSKNF_GPU_LB_REMOVE_PAIR 1u           /* flags */
+#define XSKNF_GPU_LB_REMOVED 0                /* result: sessions removed */
+#define XSKNF_GPU_LB_COMPACTED 1              /* result: 1 if the table was rebuilt free of tombstones */
+#define XSKNF_GPU_LB_REMOVE_RESULT 2
+XSKNF_GPU_API int xsknf_gpu_lb_sessions_remove(struct xsknf_gpu_lb *lb, const struct xsknf_gpu_lb_session_key *keys,
+		uint32_t n, uint32_t flags, uint64_t *result_dev, void *stream);
+XSKNF_GPU_API int xsknf_gpu_lb_sessions_remove_host(struct xsknf_gpu_lb *lb,
+		const struct xsknf_gpu_lb_session_key *keys, uint32_t n, uint32_t flags, uint64_t *result);
+XSKNF_GPU_API int xsknf_gpu_lb_drain_backend(struct xsknf_gpu_lb *lb, uint32_t addr, uint16_t port, uint8_t proto,
+		uint64_t *result_dev, void *stream);
+XSKNF_GPU_API int xsknf_gpu_lb_drain_backend_host(struct xsknf_gpu_lb *lb, uint32_t addr, uint16_t port,
+		uint8_t proto, uint64_t *result);
+XSKNF_GPU_API int xsknf_gpu_lb_sessions_clear(struct xsknf_gpu_lb *lb, int which, void *stream);
+
 /* Bytes of device workspace a batch of n frames needs (16-byte aligned, the
  * caller's, as for the router; its contents mean nothing between calls).
  * -EINVAL for a NULL bytes or n > XSKNF_GPU_LB_MAX_BATCH. */

@@ -70,6 +70,11 @@ EXPORTED_SYMBOLS = (
     "xsknf_gpu_lb_destroy",
     "xsknf_gpu_lb_sessions_put",
     "xsknf_gpu_lb_sessions_dump",
+    "xsknf_gpu_lb_sessions_remove",
+    "xsknf_gpu_lb_sessions_remove_host",
+    "xsknf_gpu_lb_drain_backend",
+    "xsknf_gpu_lb_drain_backend_host",
+    "xsknf_gpu_lb_sessions_clear",
     "xsknf_gpu_lb_workspace",
     "xsknf_gpu_lb_batch",
     "xsknf_gpu_lb_host",
@@ -85,6 +90,10 @@ LB_MAX_SESSIONS = 2000000   # XSKNF_GPU_LB_MAX_SESSIONS
 LB_MAX_SLOTS = 1 << 24      # XSKNF_GPU_LB_MAX_SLOTS
 LB_MAX_BATCH = 1 << 24      # XSKNF_GPU_LB_MAX_BATCH
 LB_STATS = 8                # XSKNF_GPU_LB_STATS
+LB_REMOVE_PAIR = 1          # XSKNF_GPU_LB_REMOVE_PAIR
+LB_REMOVED = 0              # XSKNF_GPU_LB_REMOVED, a word of a removal's result
+LB_COMPACTED = 1            # XSKNF_GPU_LB_COMPACTED
+LB_REMOVE_RESULT = 2        # XSKNF_GPU_LB_REMOVE_RESULT
 
 ACL_MAX_RULES = 1000000     # XSKNF_GPU_ACL_MAX_RULES
 ACL_MAX_SLOTS = 1 << 24     # XSKNF_GPU_ACL_MAX_SLOTS
@@ -354,6 +363,17 @@ def load() -> ctypes.CDLL:
     lib.xsknf_gpu_lb_sessions_put.argtypes = [vp, vp, vp, u32]
     lib.xsknf_gpu_lb_sessions_dump.restype = ctypes.c_int
     lib.xsknf_gpu_lb_sessions_dump.argtypes = [vp, ctypes.c_int, vp, vp, u32, ctypes.POINTER(u32)]
+    u16, u8 = ctypes.c_uint16, ctypes.c_uint8
+    lib.xsknf_gpu_lb_sessions_remove.restype = ctypes.c_int
+    lib.xsknf_gpu_lb_sessions_remove.argtypes = [vp, vp, u32, u32, vp, vp]
+    lib.xsknf_gpu_lb_sessions_remove_host.restype = ctypes.c_int
+    lib.xsknf_gpu_lb_sessions_remove_host.argtypes = [vp, vp, u32, u32, vp]
+    lib.xsknf_gpu_lb_drain_backend.restype = ctypes.c_int
+    lib.xsknf_gpu_lb_drain_backend.argtypes = [vp, u32, u16, u8, vp, vp]
+    lib.xsknf_gpu_lb_drain_backend_host.restype = ctypes.c_int
+    lib.xsknf_gpu_lb_drain_backend_host.argtypes = [vp, u32, u16, u8, vp]
+    lib.xsknf_gpu_lb_sessions_clear.restype = ctypes.c_int
+    lib.xsknf_gpu_lb_sessions_clear.argtypes = [vp, ctypes.c_int, vp]
     lib.xsknf_gpu_lb_workspace.restype = ctypes.c_int
     lib.xsknf_gpu_lb_workspace.argtypes = [u32, ctypes.POINTER(u64)]
     lib.xsknf_gpu_lb_batch.restype = ctypes.c_int

@@ -1,10 +1,13 @@
 // lb.cpp -- the load balancer's object (include/xsknf_gpu.h xsknf_gpu_lb_create,
 // _info, _destroy, _sessions_put, _sessions_dump): the service and backend
-// tables of lb_table.h built on one host thread, and the two session tables.
+// tables of lb_table.h built on one host thread, and the two session tables;
+// and the removal of sessions (_sessions_remove, _drain_backend, _sessions_clear):
+// the host table's here, the device table's checked here and handed to
+// lb_remove_device.hip.
 // Plain C++; the only GPU calls are the allocation, the uploads, the table's
 // copies for _sessions_put and _sessions_dump and the release, and a build with
-// XSKNF_LB_HOST_ONLY has none (the sanitizer program, tests/c/san_lb.c, links
-// this file and lb_host.cpp alone).
+// XSKNF_LB_HOST_ONLY has none (the sanitizer programs, tests/c/san_lb.c and
+// san_lb_remove.c, link this file and lb_host.cpp alone).
 #include <errno.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -35,6 +38,8 @@ void free_lb(xsknf_gpu_lb *lb) {
   free(lb->bk);
   free(lb->keys);
   free(lb->vals);
+  free(lb->live_k);
+  free(lb->live_v);
   delete lb;
 }
 
@@ -55,7 +60,7 @@ int dump_table(const Key *keys, const Val *vals, uint32_t slots, xsknf_gpu_lb_se
   std::vector<uint32_t> used;
   try {
     for (uint32_t s = 0; s < slots; ++s)
-      if (keys[s].p) used.push_back(s);
+      if (live(keys[s])) used.push_back(s);
   } catch (const std::bad_alloc &) {
     return -ENOMEM;
   }
@@ -98,6 +103,65 @@ int put_all(const Tables &t, const xsknf_gpu_lb_session_key *keys, const xsknf_g
   for (uint32_t i = 0; i < n; ++i)
     if (put(t, key_of(keys[i]), val_of(values[i])) < 0) return -ENOSPC;
   return 0;
+}
+
+// ---- removal from the host table --------------------------------------------------
+// The same tombstones as on the device (lb_table.h), not a backward-shift
+// delete: the two tables then agree on when a rebuild happens, so one model
+// serves both, and a removal never moves a session that it does not remove.
+
+constexpr uint32_t kRemoveFlags = XSKNF_GPU_LB_REMOVE_PAIR;
+
+// The scratch of a rebuild, made by the first removal so that none can fail
+// half way: count <= max_sessions always (put and the kernels refuse beyond it).
+int want_scratch(xsknf_gpu_lb *lb) {
+  if (lb->live_k) return 0;
+  const size_t room = lb->max_sessions ? lb->max_sessions : 1;
+  Key *k = static_cast<Key *>(malloc(sizeof(Key) * room));
+  Val *v = static_cast<Val *>(malloc(sizeof(Val) * room));
+  if (!k || !v) {
+    free(k);
+    free(v);
+    return -ENOMEM;
+  }
+  lb->live_k = k;
+  lb->live_v = v;
+  return 0;
+}
+
+void bury(xsknf_gpu_lb *lb, uint32_t s) {
+  lb->keys[s].p = kTombstoneP;
+  --lb->count;
+  ++lb->tombstones;
+}
+
+// After a removal: past the bound the live sessions are reinserted, in
+// ascending slot order, into the emptied table.  Returns 1 if it rebuilt.
+uint64_t settle(xsknf_gpu_lb *lb) {
+  if (lb->tombstones <= lb->slots / kTombstoneShare) return 0;
+  uint32_t n = 0;
+  for (uint32_t s = 0; s < lb->slots; ++s)
+    if (live(lb->keys[s])) {
+      lb->live_k[n] = lb->keys[s];
+      lb->live_v[n++] = lb->vals[s];
+    }
+  memset(lb->keys, 0, sizeof(Key) * lb->slots);
+  memset(lb->vals, 0, sizeof(Val) * lb->slots);
+  const uint32_t mask = lb->slots - 1;
+  for (uint32_t i = 0; i < n; ++i) {
+    uint32_t s = key_hash(lb->live_k[i]) & mask;
+    while (lb->keys[s].p) s = (s + 1) & mask;   // (the keys are distinct and at most half the slots)
+    lb->keys[s] = lb->live_k[i];
+    lb->vals[s] = lb->live_v[i];
+  }
+  lb->tombstones = 0;
+  return 1;
+}
+
+void report(uint64_t *result, uint64_t removed, uint64_t compacted) {
+  if (!result) return;
+  result[XSKNF_GPU_LB_REMOVED] = removed;
+  result[XSKNF_GPU_LB_COMPACTED] = compacted;
 }
 
 #ifndef XSKNF_LB_HOST_ONLY
@@ -241,12 +305,102 @@ int xsknf_gpu_lb_destroy(struct xsknf_gpu_lb *lb) {
   int rc = 0;
 #ifndef XSKNF_LB_HOST_ONLY
   if (lb->d_svc) {
+    rc = xsknf_gpu::lb_remove_release(lb);
     const hipError_t e = hipFree(lb->d_svc);
     if (e != hipSuccess) rc = hip_rc(e, "load balancer release");
   }
 #endif
   free_lb(lb);
   return rc;
+}
+
+int xsknf_gpu_lb_sessions_remove_host(struct xsknf_gpu_lb *lb, const struct xsknf_gpu_lb_session_key *keys, uint32_t n,
+                                      uint32_t flags, uint64_t *result) {
+  if (!lb || (n && !keys) || (flags & ~kRemoveFlags)) return -EINVAL;
+  report(result, 0, 0);
+  if (n == 0) return 0;
+  const int rc = want_scratch(lb);
+  if (rc) return rc;
+  // In list order.  This is the set semantics: what a key or a partner check
+  // reads of a slot -- its key words and its value -- no removal changes, and a
+  // slot is only ever buried by a listed key or by a partner that passed.
+  uint64_t removed = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (keys[i].proto != 6 && keys[i].proto != 17) continue;
+    const Key k = key_of(keys[i]);
+    const uint32_t s = find(lb->keys, lb->slots, k);
+    if (s == kNone) continue;
+    const Val v = lb->vals[s];
+    bury(lb, s);
+    ++removed;
+    if (!(flags & XSKNF_GPU_LB_REMOVE_PAIR)) continue;
+    const Key pk = partner_key(k, v);
+    const uint32_t ps = find(lb->keys, lb->slots, pk);
+    if (ps != kNone && is_partner(pk, lb->vals[ps], k, v)) {
+      bury(lb, ps);
+      ++removed;
+    }
+  }
+  report(result, removed, settle(lb));
+  return 0;
+}
+
+int xsknf_gpu_lb_drain_backend_host(struct xsknf_gpu_lb *lb, uint32_t addr, uint16_t port, uint8_t proto,
+                                    uint64_t *result) {
+  if (!lb || (proto != 6 && proto != 17)) return -EINVAL;
+  report(result, 0, 0);
+  const int rc = want_scratch(lb);
+  if (rc) return rc;
+  uint64_t removed = 0;
+  for (uint32_t s = 0; s < lb->slots; ++s)
+    if (drains(lb->keys[s], lb->vals[s], addr, port, proto)) {
+      bury(lb, s);
+      ++removed;
+    }
+  report(result, removed, settle(lb));
+  return 0;
+}
+
+int xsknf_gpu_lb_sessions_remove(struct xsknf_gpu_lb *lb, const struct xsknf_gpu_lb_session_key *keys, uint32_t n,
+                                 uint32_t flags, uint64_t *result_dev, void *stream) {
+  if (!lb || (n && !keys) || (flags & ~kRemoveFlags) || (reinterpret_cast<uintptr_t>(result_dev) & 7)) return -EINVAL;
+  if (!lb->d_svc) return -ENODEV;
+#ifndef XSKNF_LB_HOST_ONLY
+  return xsknf_gpu::lb_remove_enqueue(lb, keys, n, (flags & XSKNF_GPU_LB_REMOVE_PAIR) != 0, result_dev, stream);
+#else
+  (void)stream;
+  return -ENODEV;
+#endif
+}
+
+int xsknf_gpu_lb_drain_backend(struct xsknf_gpu_lb *lb, uint32_t addr, uint16_t port, uint8_t proto,
+                               uint64_t *result_dev, void *stream) {
+  if (!lb || (proto != 6 && proto != 17) || (reinterpret_cast<uintptr_t>(result_dev) & 7)) return -EINVAL;
+  if (!lb->d_svc) return -ENODEV;
+#ifndef XSKNF_LB_HOST_ONLY
+  return xsknf_gpu::lb_drain_enqueue(lb, addr, port, proto, result_dev, stream);
+#else
+  (void)addr, (void)port, (void)stream;
+  return -ENODEV;
+#endif
+}
+
+int xsknf_gpu_lb_sessions_clear(struct xsknf_gpu_lb *lb, int which, void *stream) {
+  if (!lb || (which != XSKNF_GPU_LB_HOST_TABLE && which != XSKNF_GPU_LB_DEVICE_TABLE)) return -EINVAL;
+  if (which == XSKNF_GPU_LB_HOST_TABLE) {
+    memset(lb->keys, 0, sizeof(Key) * lb->slots);
+    memset(lb->vals, 0, sizeof(Val) * lb->slots);
+    lb->count = 0;
+    lb->tombstones = 0;
+    return 0;
+  }
+  if (!lb->d_svc) return -ENODEV;
+#ifndef XSKNF_LB_HOST_ONLY
+  return xsknf_gpu::lb_clear_enqueue(lb, stream);
+#else
+  (void)stream;
+  return -ENODEV;
+#endif
 }
 
 int xsknf_gpu_lb_sessions_put(struct xsknf_gpu_lb *lb, const struct xsknf_gpu_lb_session_key *keys,

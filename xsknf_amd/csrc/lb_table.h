@@ -13,8 +13,18 @@
 //   a = saddr, b = daddr, c = sport | dport << 16, p = proto (0: empty slot)
 // and vals[s], 16 bytes, belongs to it:
 //   addr, pi = port | ifindex << 16, m0 = mac[0..3], m1 = mac[4..5] | dir << 16.
-// Nothing is ever deleted, so a probe ends at the key or at the first empty
-// slot, and the builder keeps slots >= 2 * max_sessions.
+// A probe ends at the key or at the first empty slot, and the builder keeps
+// slots >= 2 * max_sessions.
+//
+// Removal (xsknf_gpu_lb_sessions_remove, _drain_backend; lb.cpp on the host,
+// kernel_lb_remove.h on the device) overwrites a slot's p with kTombstoneP, the
+// ACL's tombstone, and leaves its other words: p is not 0, so find, put and the
+// batch kernels walk on over it, and it is not 6 or 17, so no key equals it --
+// none of them has a word about it.  put and the kernels' commit_one take empty
+// slots only, so tombstones pile up until a removal leaves more than slots /
+// kTombstoneShare of them; that removal rebuilds the table tombstone-free.
+// Live sessions (<= max_sessions <= slots / 2) plus tombstones (<= slots / 4)
+// thus never pass 3/4 of the slots: every probe sequence keeps an empty slot.
 // The services are a table of the same kind, {vaddr, vport | proto << 16} ->
 // {first, count}: the service's backends are bk[first .. first + count) in the
 // order their records were given.
@@ -28,6 +38,8 @@ namespace lb {
 
 constexpr uint32_t kToClient = 0, kToBackend = 1;   // enum direction, load_balancer.h:41-44
 constexpr uint32_t kNone = 0xffffffffu;
+constexpr uint32_t kTombstoneP = kAclTombstoneP;   // p of a removed slot
+constexpr uint32_t kTombstoneShare = 4;            // a removal that leaves more than slots / 4 tombstones rebuilds
 
 struct Key {
   uint32_t a, b, c, p;
@@ -94,6 +106,33 @@ XSKNF_HD inline int put(const Tables &t, const Key &k, const Val &v) {
     s = (s + 1) & mask;
   }
   return -1;
+}
+
+// ---- removal: what lb.cpp and kernel_lb_remove.h share ---------------------------
+XSKNF_HD inline bool live(const Key &k) { return k.p != 0 && k.p != kTombstoneP; }
+XSKNF_HD inline uint32_t dir_of(const Val &v) { return v.m1 >> 16 & 0xff; }
+// The key of the other half of the flow that session {k -> v} belongs to: for a
+// TO_BACKEND session {saddr, daddr, sport, dport} -> {addr, port} it is
+// backward_key's {addr, saddr, port, sport}, for a TO_CLIENT one {daddr, addr,
+// dport, port}.  k.p is the session's protocol (6 or 17), also where the slot
+// itself has just been made a tombstone.
+XSKNF_HD inline Key partner_key(const Key &k, const Val &v) {
+  const uint32_t port = v.pi & 0xffff;
+  if (dir_of(v) == kToBackend) return Key{v.addr, k.a, port | (k.c & 0xffff) << 16, k.p};
+  return Key{k.b, v.addr, (k.c >> 16) | port << 16, k.p};
+}
+// Whether the stored session {pk -> pv} is the partner of {k -> v}, given that
+// pk == partner_key(k, v): the opposite direction, and its own partner is k.
+// An unpaired sessions_put entry, or a backward session that another flow has
+// replaced, fails this and stays.
+XSKNF_HD inline bool is_partner(const Key &pk, const Val &pv, const Key &k, const Val &v) {
+  return dir_of(pv) != dir_of(v) && same(partner_key(pk, pv), k);
+}
+// drain_backend's predicate for one slot: both halves of every flow of backend
+// {addr, port, proto} (proto is 6 or 17, so an empty slot and a tombstone fail).
+XSKNF_HD inline bool drains(const Key &k, const Val &v, uint32_t addr, uint32_t port, uint32_t proto) {
+  if (k.p != proto) return false;
+  return dir_of(v) == kToBackend ? v.addr == addr && (v.pi & 0xffff) == port : k.a == addr && (k.c & 0xffff) == port;
 }
 
 // The service {vaddr, vport, proto}, or NULL.
@@ -318,11 +357,30 @@ struct xsknf_gpu_lb {
   xsknf_gpu::lb::Key *keys;
   xsknf_gpu::lb::Val *vals;
   uint32_t count;
+  uint32_t tombstones;                 // host table: slots that hold kTombstoneP
+  xsknf_gpu::lb::Key *live_k;          // host: room for max_sessions sessions while the table is rebuilt
+  xsknf_gpu::lb::Val *live_v;          //   (NULL until the first host removal)
   // device (all NULL in a host-only object): one allocation, d_svc first
   xsknf_gpu::lb::Service *d_svc;
   xsknf_gpu::lb::Backend *d_bk;
   xsknf_gpu::lb::Key *d_keys;
   xsknf_gpu::lb::Val *d_vals;
-  uint32_t *d_count;
+  uint32_t *d_count;                   // d_count[1]: the device table's tombstones
   uint64_t device_bytes;
+  // lb_remove_device.hip (NULL until the first device removal): the spare table
+  // a compaction rebuilds into, keys then values, and the key lists' buffers
+  xsknf_gpu::lb::Key *d_spare;
+  struct xsknf_gpu_lb_staging *staging;
 };
+
+#ifndef XSKNF_LB_HOST_ONLY
+// lb_remove_device.hip: the removals on the device table, enqueued on `stream`
+// (lb.cpp has validated the arguments and the object has a device half).  All
+// return 0, -ENOMEM or -EIO (xsknf_gpu_last_error()).
+namespace xsknf_gpu {
+int lb_remove_enqueue(xsknf_gpu_lb *lb, const void *keys, uint32_t n, bool pair, uint64_t *result_dev, void *stream);
+int lb_drain_enqueue(xsknf_gpu_lb *lb, uint32_t addr, uint32_t port, uint32_t proto, uint64_t *result_dev, void *stream);
+int lb_clear_enqueue(xsknf_gpu_lb *lb, void *stream);
+int lb_remove_release(xsknf_gpu_lb *lb);   // _destroy
+}  // namespace xsknf_gpu
+#endif

@@ -13,7 +13,10 @@ device that was current when it was made.  `lb_batch` runs a batch on the device
 for a UMEM and descriptors that lie there (xsknf_gpu_lb_batch;
 xsknf_amd/csrc/lb_device.hip), `lb_host` on one CPU thread (xsknf_gpu_lb_host:
 the model the device is held to).  Both rewrite the UMEM in place; the verdicts
-are what route.route_batch consumes.
+are what route.route_batch consumes.  Sessions end through
+`LoadBalancer.sessions_remove`, `drain_backend` and `sessions_clear`
+(xsknf_amd/csrc/lb_remove_device.hip for the device table): on the device they
+are enqueued between batches and wait for nothing.
 """
 from __future__ import annotations
 
@@ -117,6 +120,68 @@ class LoadBalancer:
             _lib.check(lib.xsknf_gpu_lb_sessions_dump(self.handle, which, k.ctypes.data, v.ctypes.data, k.size,
                                                       ctypes.byref(n)), "xsknf_gpu_lb_sessions_dump")
         return k, v
+
+    def _device_result(self, stream):
+        """(result tensor, stream handle) of a device removal: two int64 words
+        on the current device, and `stream` (a torch stream, a raw handle, or
+        None for the current stream)."""
+        import torch
+
+        res = torch.empty(_lib.LB_REMOVE_RESULT, dtype=torch.int64, device=torch.device("cuda", torch.cuda.current_device()))
+        if stream is None:
+            stream = torch.cuda.current_stream()
+        return res, int(getattr(stream, "cuda_stream", stream))
+
+    def sessions_remove(self, keys, *, pair: bool = False, which: int = DEVICE_TABLE, stream=None):
+        """xsknf_gpu_lb_sessions_remove (which == DEVICE_TABLE) or _remove_host:
+        the listed KEY_DTYPE records leave one session table, with `pair` also
+        each one's partner -- the other half of its flow -- where the table
+        holds it as such.  Returns the two result words (REMOVED, COMPACTED):
+        for the host table a uint64 array; for the device table an int64
+        device tensor that is written on `stream` (default: the current
+        stream of the current device, which must be the object's) -- nothing
+        waits for it."""
+        k = _records(keys, 16, "keys")
+        flags = _lib.LB_REMOVE_PAIR if pair else 0
+        kp = k.ctypes.data if k.size else None
+        if which == HOST_TABLE:
+            res = np.zeros(_lib.LB_REMOVE_RESULT, dtype=np.uint64)
+            _lib.check(_lib.load().xsknf_gpu_lb_sessions_remove_host(self.handle, kp, k.size, flags, res.ctypes.data),
+                       "xsknf_gpu_lb_sessions_remove_host")
+            return res
+        if which != DEVICE_TABLE:
+            raise ValueError("which must be HOST_TABLE or DEVICE_TABLE")
+        res, s = self._device_result(stream)
+        _lib.check(_lib.load().xsknf_gpu_lb_sessions_remove(self.handle, kp, k.size, flags, res.data_ptr(),
+                                                            ctypes.c_void_p(s or None)), "xsknf_gpu_lb_sessions_remove")
+        return res
+
+    def drain_backend(self, addr: int, port: int, proto: int, *, which: int = DEVICE_TABLE, stream=None):
+        """xsknf_gpu_lb_drain_backend / _drain_backend_host: both halves of
+        every flow of backend (addr, port, proto) leave one session table.
+        Returns the result words as `sessions_remove` does."""
+        if which == HOST_TABLE:
+            res = np.zeros(_lib.LB_REMOVE_RESULT, dtype=np.uint64)
+            _lib.check(_lib.load().xsknf_gpu_lb_drain_backend_host(self.handle, addr, port, proto, res.ctypes.data),
+                       "xsknf_gpu_lb_drain_backend_host")
+            return res
+        if which != DEVICE_TABLE:
+            raise ValueError("which must be HOST_TABLE or DEVICE_TABLE")
+        res, s = self._device_result(stream)
+        _lib.check(_lib.load().xsknf_gpu_lb_drain_backend(self.handle, addr, port, proto, res.data_ptr(),
+                                                          ctypes.c_void_p(s or None)), "xsknf_gpu_lb_drain_backend")
+        return res
+
+    def sessions_clear(self, which: int, *, stream=None) -> None:
+        """xsknf_gpu_lb_sessions_clear: every session of one table; the device
+        table's on `stream` (default: the current stream), waiting for nothing."""
+        s = 0
+        if which == DEVICE_TABLE:
+            import torch
+
+            s = int(getattr(stream, "cuda_stream", stream)) if stream is not None else torch.cuda.current_stream().cuda_stream
+        _lib.check(_lib.load().xsknf_gpu_lb_sessions_clear(self.handle, which, ctypes.c_void_p(s or None)),
+                   "xsknf_gpu_lb_sessions_clear")
 
     def close(self) -> None:
         if self._h:
