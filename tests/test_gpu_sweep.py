@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from oracle import csum_oracle as O
+from tests import staged_cases as SC
 from tests import sweep_cases as S
 from xsknf_amd import Checksummer, ChecksummerOptions, frames
 
@@ -298,7 +299,8 @@ def test_length_sweep_staged_split(dev):
     b, at, vals, ov = _case(("length", S.boundaries((16, 2, 2, 0, 18, 1, 56))), 1)
     gv, gu, st = _host_path(b, "staged", 4096)
     _same(b, at, vals, ov, gu, gv, "staged")
-    assert st["bytes_h2d"] >= int(b.descs["len"].sum())
+    assert st["bytes_h2d"] == sum(SC.counters(b.descs[lo:lo + 4096], b.umem.size, 4096)[0]
+                                  for lo in range(0, b.n, 4096))
 
 
 def test_length_sweep_resident(dev):
