@@ -9,7 +9,8 @@ SRCS := xsknf_amd/csrc/checksummer.hip xsknf_amd/csrc/host_path.hip xsknf_amd/cs
 	xsknf_amd/csrc/forward_host.cpp xsknf_amd/csrc/acl.cpp xsknf_amd/csrc/firewall_device.hip \
 	xsknf_amd/csrc/firewall_host.cpp xsknf_amd/csrc/lb.cpp xsknf_amd/csrc/lb_device.hip xsknf_amd/csrc/lb_host.cpp \
 	xsknf_amd/csrc/lbfw_host.cpp xsknf_amd/csrc/macswap_device.hip xsknf_amd/csrc/macswap_host.cpp \
-	xsknf_amd/csrc/acl_update_device.hip xsknf_amd/csrc/lb_remove_device.hip
+	xsknf_amd/csrc/acl_update_device.hip xsknf_amd/csrc/lb_remove_device.hip \
+	xsknf_amd/csrc/lb_backends_device.hip
 # every header the device code may include: checksummer.hip is one translation
 # unit over csum_device.h and the kernel_*.h families
 GPUHDRS := include/xsknf_gpu.h include/xsknf.h $(wildcard xsknf_amd/csrc/*.h)

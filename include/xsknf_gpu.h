@@ -963,7 +963,8 @@ XSKNF_GPU_API int xsknf_gpu_lb_sessions_dump(const struct xsknf_gpu_lb *lb, int 
  *
  * _drain_backend: every TO_BACKEND session whose value is {addr, port} and every
  * TO_CLIENT session whose key's source is {addr, port}, of protocol proto: both
- * halves of every flow of that backend.  The backend stays in its service.
+ * halves of every flow of that backend.  The backend stays in its service
+ * (xsknf_gpu_lb_backends_update takes it out).
  *
  * _sessions_clear: every session of one table (`which` as for _sessions_dump;
  * stream is used for the device table only).
@@ -993,6 +994,91 @@ XSKNF_GPU_API int xsknf_gpu_lb_drain_backend(struct xsknf_gpu_lb *lb, uint32_t a
 XSKNF_GPU_API int xsknf_gpu_lb_drain_backend_host(struct xsknf_gpu_lb *lb, uint32_t addr, uint16_t port,
 		uint8_t proto, uint64_t *result);
 XSKNF_GPU_API int xsknf_gpu_lb_sessions_clear(struct xsknf_gpu_lb *lb, int which, void *stream);
+
+/* The services and backends of a live object.  The object's services are the
+ * ordered record list xsknf_gpu_lb_create was given; the n ops edit that list
+ * in index order.
+ *   ADD     if the record's service {vaddr, vport, proto} holds one or more
+ *           backends with the record's {addr, port}, their mac and ifindex are
+ *           replaced and their backend numbers stay.  Otherwise the record is
+ *           appended as the last backend of its service; a service that does
+ *           not exist is created.
+ *   REMOVE  every backend {addr, port} of that service is removed and the
+ *           service's later backends move down by one number each.  An absent
+ *           backend or service is no error; mac and ifindex are ignored.  A
+ *           service left with no backend ceases to exist: rule 8 then passes
+ *           its new flows.
+ * After the call the object behaves, for every later batch, exactly as one made
+ * by xsknf_gpu_lb_create from the edited list: the same backend numbers feed
+ * rule 9's jhash % backends.  The order of services among themselves shows
+ * nowhere.  Neither session table is touched: a stored session keeps the addr,
+ * port, mac and ifindex it was stored with, and the flows of a removed backend
+ * go on until they are drained (xsknf_gpu_lb_drain_backends below).
+ *
+ * Host and device, as for xsknf_gpu_acl_update: the host copy is new before the
+ * call returns -- xsknf_gpu_lb_host, xsknf_gpu_lbfw_host and xsknf_gpu_lb_info
+ * (services, backends) see it at once -- and the device copy is updated
+ * asynchronously on `stream`, on the device the object was made on.  A batch of
+ * either NF enqueued on that stream before the call sees the old services, one
+ * enqueued after it the new ones; other streams are the caller's to order with
+ * an event.  The call waits for nothing (the allocations of a first call
+ * excepted).  ops is not referenced after the return: what the stream needs is
+ * copied into pinned buffers that belong to the object, one per update in
+ * flight, reused once the stream has passed it and freed by
+ * xsknf_gpu_lb_destroy.  The first update of an object with a device half
+ * allocates a region for the largest tables (2 * XSKNF_GPU_LB_MAX_SERVICES
+ * service slots and XSKNF_GPU_LB_MAX_BACKENDS backends, 2.03 MiB), from then on
+ * part of device_bytes; the tables of creation stay allocated until _destroy,
+ * for the batches that were enqueued before.  A host-only object updates its
+ * host copy and ignores stream.
+ *
+ * Everything is validated before anything changes.  -EINVAL: a NULL lb, a NULL
+ * ops with n > 0, an op other than 0 and 1, a proto other than 6 and 17 (ADD or
+ * REMOVE).  -ENOSPC: the list after all ops would hold more than
+ * XSKNF_GPU_LB_MAX_BACKENDS records or more than XSKNF_GPU_LB_MAX_SERVICES
+ * services.  -ENOMEM.  In all these cases neither copy changes.  n == 0
+ * succeeds and launches nothing.  -EIO on a HIP error (xsknf_gpu_last_error()):
+ * the host copy is new, the device copy may not be; destroy the object.
+ *
+ * _backends_dump: the records of the host copy (which ==
+ * XSKNF_GPU_LB_HOST_TABLE) or of the device copy (_DEVICE_TABLE: waits for the
+ * device, reads its two tables back and decodes them), services ascending by
+ * {vaddr, vport | proto << 16} compared as numbers, each service's backends by
+ * number, pads 0.  cap, n_out, -ENOSPC and -ENODEV are as for _sessions_dump.
+ * Once the stream has passed an update the two dumps are equal.
+ *
+ * _drain_backends: the union, over the n listed backends, of what
+ * _drain_backend removes -- both halves of every flow of each -- on the table as
+ * it stands when the stream reaches the call, in ONE pass over the table
+ * whatever n is.  Duplicates count once; pad is ignored.  The result words, the
+ * tombstones, the rebuild past slots / 4 and the first device removal's spare
+ * table are the other removals'; so are the errors and n == 0, plus -EINVAL for
+ * a listed proto other than 6 and 17 and for n > XSKNF_GPU_LB_MAX_BACKENDS.
+ * list is not referenced after the return.
+ *
+ * Taking backends out of service: _backends_update (REMOVE) first, then
+ * _drain_backends on the same stream.  No batch between the two can then open a
+ * new flow to a backend that has already been drained. */
+#define XSKNF_GPU_LB_BACKEND_ADD 0u
+#define XSKNF_GPU_LB_BACKEND_REMOVE 1u
+struct xsknf_gpu_lb_backend_op {
+	struct xsknf_gpu_lb_backend backend;
+	uint32_t op;
+};
+struct xsknf_gpu_lb_backend_id {
+	uint32_t addr;           /* network order */
+	uint16_t port;           /* network order */
+	uint8_t proto;           /* 6 or 17 */
+	uint8_t pad;             /* ignored */
+};
+XSKNF_GPU_API int xsknf_gpu_lb_backends_update(struct xsknf_gpu_lb *lb,
+		const struct xsknf_gpu_lb_backend_op *ops, uint32_t n, void *stream);
+XSKNF_GPU_API int xsknf_gpu_lb_backends_dump(const struct xsknf_gpu_lb *lb, int which,
+		struct xsknf_gpu_lb_backend *records, uint32_t cap, uint32_t *n_out);
+XSKNF_GPU_API int xsknf_gpu_lb_drain_backends(struct xsknf_gpu_lb *lb, const struct xsknf_gpu_lb_backend_id *list,
+		uint32_t n, uint64_t *result_dev, void *stream);
+XSKNF_GPU_API int xsknf_gpu_lb_drain_backends_host(struct xsknf_gpu_lb *lb,
+		const struct xsknf_gpu_lb_backend_id *list, uint32_t n, uint64_t *result);
 
 /* Bytes of device workspace a batch of n frames needs (16-byte aligned, the
  * caller's, as for the router; its contents mean nothing between calls).

@@ -75,6 +75,10 @@ EXPORTED_SYMBOLS = (
     "xsknf_gpu_lb_drain_backend",
     "xsknf_gpu_lb_drain_backend_host",
     "xsknf_gpu_lb_sessions_clear",
+    "xsknf_gpu_lb_backends_update",
+    "xsknf_gpu_lb_backends_dump",
+    "xsknf_gpu_lb_drain_backends",
+    "xsknf_gpu_lb_drain_backends_host",
     "xsknf_gpu_lb_workspace",
     "xsknf_gpu_lb_batch",
     "xsknf_gpu_lb_host",
@@ -94,6 +98,8 @@ LB_REMOVE_PAIR = 1          # XSKNF_GPU_LB_REMOVE_PAIR
 LB_REMOVED = 0              # XSKNF_GPU_LB_REMOVED, a word of a removal's result
 LB_COMPACTED = 1            # XSKNF_GPU_LB_COMPACTED
 LB_REMOVE_RESULT = 2        # XSKNF_GPU_LB_REMOVE_RESULT
+LB_BACKEND_ADD = 0          # XSKNF_GPU_LB_BACKEND_ADD, the op of struct xsknf_gpu_lb_backend_op
+LB_BACKEND_REMOVE = 1       # XSKNF_GPU_LB_BACKEND_REMOVE
 
 ACL_MAX_RULES = 1000000     # XSKNF_GPU_ACL_MAX_RULES
 ACL_MAX_SLOTS = 1 << 24     # XSKNF_GPU_ACL_MAX_SLOTS
@@ -374,6 +380,14 @@ def load() -> ctypes.CDLL:
     lib.xsknf_gpu_lb_drain_backend_host.argtypes = [vp, u32, u16, u8, vp]
     lib.xsknf_gpu_lb_sessions_clear.restype = ctypes.c_int
     lib.xsknf_gpu_lb_sessions_clear.argtypes = [vp, ctypes.c_int, vp]
+    lib.xsknf_gpu_lb_backends_update.restype = ctypes.c_int
+    lib.xsknf_gpu_lb_backends_update.argtypes = [vp, vp, u32, vp]
+    lib.xsknf_gpu_lb_backends_dump.restype = ctypes.c_int
+    lib.xsknf_gpu_lb_backends_dump.argtypes = [vp, ctypes.c_int, vp, u32, ctypes.POINTER(u32)]
+    lib.xsknf_gpu_lb_drain_backends.restype = ctypes.c_int
+    lib.xsknf_gpu_lb_drain_backends.argtypes = [vp, vp, u32, vp, vp]
+    lib.xsknf_gpu_lb_drain_backends_host.restype = ctypes.c_int
+    lib.xsknf_gpu_lb_drain_backends_host.argtypes = [vp, vp, u32, vp]
     lib.xsknf_gpu_lb_workspace.restype = ctypes.c_int
     lib.xsknf_gpu_lb_workspace.argtypes = [u32, ctypes.POINTER(u64)]
     lib.xsknf_gpu_lb_batch.restype = ctypes.c_int

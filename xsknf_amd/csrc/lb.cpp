@@ -3,7 +3,10 @@
 // tables of lb_table.h built on one host thread, and the two session tables;
 // and the removal of sessions (_sessions_remove, _drain_backend, _sessions_clear):
 // the host table's here, the device table's checked here and handed to
-// lb_remove_device.hip.
+// lb_remove_device.hip; and the services and backends of a live object
+// (_backends_update, _backends_dump) and the list drain (_drain_backends): the
+// ordered list is edited and the tables rebuilt here, what changed goes to
+// lb_backends_device.hip.
 // Plain C++; the only GPU calls are the allocation, the uploads, the table's
 // copies for _sessions_put and _sessions_dump and the release, and a build with
 // XSKNF_LB_HOST_ONLY has none (the sanitizer programs, tests/c/san_lb.c and
@@ -14,7 +17,9 @@
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 #include <new>
+#include <unordered_map>
 #include <vector>
 
 #include "lb_table.h"
@@ -29,6 +34,18 @@ void set_error(hipError_t e, const char *where);   // checksummer.hip
 }
 #endif
 
+// The record list the object stands for: the services in the order they came to
+// be (a service that lost its last backend and returns comes last), each with
+// its backends by number.  The order of the services shows in the layout of
+// svc and bk alone, never in a result.
+struct xsknf_gpu_lb_list {
+  struct Svc {
+    uint32_t vaddr, vp;
+    std::vector<xsknf_gpu::lb::Backend> bk;
+  };
+  std::vector<Svc> svcs;
+};
+
 namespace {
 
 using namespace xsknf_gpu::lb;
@@ -36,6 +53,7 @@ using namespace xsknf_gpu::lb;
 void free_lb(xsknf_gpu_lb *lb) {
   free(lb->svc);
   free(lb->bk);
+  delete lb->list;
   free(lb->keys);
   free(lb->vals);
   free(lb->live_k);
@@ -164,6 +182,141 @@ void report(uint64_t *result, uint64_t removed, uint64_t compacted) {
   result[XSKNF_GPU_LB_COMPACTED] = compacted;
 }
 
+// ---- the services and backends ------------------------------------------------------
+inline uint32_t vp_of(const xsknf_gpu_lb_backend &r) {
+  return static_cast<uint32_t>(r.vport) | static_cast<uint32_t>(r.proto) << 16;
+}
+inline uint64_t svc_id(uint32_t vaddr, uint32_t vp) { return static_cast<uint64_t>(vaddr) << 32 | vp; }
+inline Backend backend_of_record(const xsknf_gpu_lb_backend &r) {
+  return Backend{r.addr, static_cast<uint32_t>(r.port) | static_cast<uint32_t>(r.ifindex) << 16, mac_lo(r.mac),
+                 mac_hi(r.mac)};
+}
+inline uint32_t total_of(const xsknf_gpu_lb_list &l) {
+  size_t t = 0;
+  for (const auto &s : l.svcs) t += s.bk.size();
+  return static_cast<uint32_t>(t);   // (the callers have bounded it)
+}
+
+// The two tables of a list (at most half of svc_slots services): every service,
+// in the list's order, into the first empty slot from its home, its backends
+// behind those of the services before it.  Nothing else decides the layout, so
+// an object made from a list and one edited into it hold the same tables.
+bool build_tables(const xsknf_gpu_lb_list &l, uint32_t svc_slots, Service **svc_out, Backend **bk_out) {
+  const uint32_t total = total_of(l);
+  Service *svc = static_cast<Service *>(calloc(svc_slots, sizeof(Service)));
+  Backend *bk = static_cast<Backend *>(calloc(total ? total : 1, sizeof(Backend)));
+  if (!svc || !bk) {
+    free(svc);
+    free(bk);
+    return false;
+  }
+  const uint32_t mask = svc_slots - 1;
+  uint32_t first = 0;
+  for (const auto &e : l.svcs) {
+    uint32_t s = xsknf_gpu::acl_hash(e.vaddr, e.vp, 0, 0) & mask;
+    while (svc[s].count) s = (s + 1) & mask;
+    const uint32_t count = static_cast<uint32_t>(e.bk.size());
+    svc[s] = Service{e.vaddr, e.vp, first, count};
+    memcpy(bk + first, e.bk.data(), sizeof(Backend) * count);
+    first += count;
+  }
+  *svc_out = svc;
+  *bk_out = bk;
+  return true;
+}
+
+// The records of a pair of tables, ascending by service, a service's by number.
+int dump_services(const Service *svc, uint32_t svc_slots, const Backend *bk, uint32_t total,
+                  xsknf_gpu_lb_backend *out, uint32_t cap, uint32_t *n_out) {
+  std::vector<Service> used;
+  try {
+    for (uint32_t s = 0; s < svc_slots; ++s)
+      if (svc[s].count) used.push_back(svc[s]);
+  } catch (const std::bad_alloc &) {
+    return -ENOMEM;
+  }
+  std::sort(used.begin(), used.end(), [](const Service &x, const Service &y) {
+    return x.vaddr != y.vaddr ? x.vaddr < y.vaddr : x.vp < y.vp;
+  });
+  uint64_t n = 0;
+  for (const Service &e : used) {
+    if (e.first > total || e.count > total - e.first) return -EIO;   // not a table of this object
+    for (uint32_t k = 0; k < e.count; ++k, ++n) {
+      if (n >= cap) continue;
+      const Backend &b = bk[e.first + k];
+      xsknf_gpu_lb_backend r;
+      memset(&r, 0, sizeof(r));
+      r.vaddr = e.vaddr;
+      r.vport = static_cast<uint16_t>(e.vp);
+      r.proto = static_cast<uint8_t>(e.vp >> 16);
+      r.addr = b.addr;
+      r.port = static_cast<uint16_t>(b.pi);
+      r.ifindex = static_cast<uint16_t>(b.pi >> 16);
+      for (int i = 0; i < 4; ++i) r.mac[i] = static_cast<uint8_t>(b.m0 >> (8 * i));
+      r.mac[4] = static_cast<uint8_t>(b.m1);
+      r.mac[5] = static_cast<uint8_t>(b.m1 >> 8);
+      out[n] = r;
+    }
+  }
+  *n_out = static_cast<uint32_t>(n);
+  return n > cap ? -ENOSPC : 0;
+}
+
+// The ops on a copy of the list, in index order (the caller has validated them).
+void edit_list(xsknf_gpu_lb_list &l, const xsknf_gpu_lb_backend_op *ops, uint32_t n) {
+  std::unordered_map<uint64_t, uint32_t> at;
+  for (uint32_t k = 0; k < l.svcs.size(); ++k) at.emplace(svc_id(l.svcs[k].vaddr, l.svcs[k].vp), k);
+  for (uint32_t i = 0; i < n; ++i) {
+    const xsknf_gpu_lb_backend &r = ops[i].backend;
+    const uint32_t vp = vp_of(r);
+    const auto it = at.find(svc_id(r.vaddr, vp));
+    const auto is_it = [&r](const Backend &b) { return b.addr == r.addr && (b.pi & 0xffff) == r.port; };
+    if (ops[i].op == XSKNF_GPU_LB_BACKEND_REMOVE) {
+      if (it == at.end()) continue;
+      auto &bk = l.svcs[it->second].bk;
+      bk.erase(std::remove_if(bk.begin(), bk.end(), is_it), bk.end());
+      if (bk.empty()) at.erase(it);   // the service is gone: an ADD makes a new one, last
+      continue;
+    }
+    const Backend nb = backend_of_record(r);
+    if (it == at.end()) {
+      at.emplace(svc_id(r.vaddr, vp), static_cast<uint32_t>(l.svcs.size()));
+      l.svcs.push_back(xsknf_gpu_lb_list::Svc{r.vaddr, vp, {nb}});
+      continue;
+    }
+    auto &bk = l.svcs[it->second].bk;
+    bool found = false;
+    for (Backend &b : bk)
+      if (is_it(b)) {
+        b = nb;
+        found = true;
+      }
+    if (!found) bk.push_back(nb);
+  }
+  l.svcs.erase(std::remove_if(l.svcs.begin(), l.svcs.end(), [](const xsknf_gpu_lb_list::Svc &s) { return s.bk.empty(); }),
+               l.svcs.end());
+}
+
+// The listed backends as lb_table.h's set; duplicates fall together.
+void id_set_of(const xsknf_gpu_lb_backend_id *list, uint32_t n, std::vector<IdSlot> &set) {
+  uint32_t slots = 2;
+  while (slots < 2 * n) slots *= 2;
+  set.assign(slots, IdSlot{0, 0});
+  for (uint32_t i = 0; i < n; ++i) {
+    const IdSlot c = {list[i].addr, static_cast<uint32_t>(list[i].port) | static_cast<uint32_t>(list[i].proto) << 16};
+    uint32_t s = xsknf_gpu::acl_hash(c.addr, c.pw, 0, 0) & (slots - 1);
+    while (set[s].pw && !(set[s].addr == c.addr && set[s].pw == c.pw)) s = (s + 1) & (slots - 1);
+    set[s] = c;
+  }
+}
+
+int drain_list_args(const xsknf_gpu_lb *lb, const xsknf_gpu_lb_backend_id *list, uint32_t n) {
+  if (!lb || (n && !list) || n > XSKNF_GPU_LB_MAX_BACKENDS) return -EINVAL;
+  for (uint32_t i = 0; i < n; ++i)
+    if (list[i].proto != 6 && list[i].proto != 17) return -EINVAL;
+  return 0;
+}
+
 #ifndef XSKNF_LB_HOST_ONLY
 int hip_rc(hipError_t e, const char *where) {
   xsknf_gpu::set_error(e, where);
@@ -193,59 +346,42 @@ int xsknf_gpu_lb_create(struct xsknf_gpu_lb **lb_out, const struct xsknf_gpu_lb_
   lb->max_sessions = max_sessions;
   lb->svc_slots = 2 * XSKNF_GPU_LB_MAX_SERVICES;   // at most half full
   lb->backends = n;
-  lb->svc = static_cast<Service *>(calloc(lb->svc_slots, sizeof(Service)));
-  lb->bk = static_cast<Backend *>(calloc(n ? n : 1, sizeof(Backend)));
   lb->keys = static_cast<Key *>(calloc(slots, sizeof(Key)));
   lb->vals = static_cast<Val *>(calloc(slots, sizeof(Val)));
-  uint32_t *order = static_cast<uint32_t *>(calloc(XSKNF_GPU_LB_MAX_SERVICES, sizeof(uint32_t)));
-  if (!lb->svc || !lb->bk || !lb->keys || !lb->vals || !order) {
-    free(order);
+  lb->list = new (std::nothrow) xsknf_gpu_lb_list();
+  if (!lb->keys || !lb->vals || !lb->list) {
     free_lb(lb);
     return -ENOMEM;
   }
-  // pass 1: the services in the order they first appear, with their backend counts
-  const uint32_t smask = lb->svc_slots - 1;
-  auto slot_of = [&](const xsknf_gpu_lb_backend &r, uint32_t vp) {
-    uint32_t s = xsknf_gpu::acl_hash(r.vaddr, vp, 0, 0) & smask;
-    while (lb->svc[s].count && !(lb->svc[s].vaddr == r.vaddr && lb->svc[s].vp == vp)) s = (s + 1) & smask;
-    return s;
-  };
-  for (uint32_t i = 0; i < n; ++i) {
-    const xsknf_gpu_lb_backend &r = backends[i];
-    const uint32_t vp = static_cast<uint32_t>(r.vport) | static_cast<uint32_t>(r.proto) << 16;
-    const uint32_t s = slot_of(r, vp);
-    if (!lb->svc[s].count) {
-      if (lb->services == XSKNF_GPU_LB_MAX_SERVICES) {
-        free(order);
-        free_lb(lb);
-        return -EINVAL;
+  // the services in the order they first appear, each with its records in order
+  try {
+    std::unordered_map<uint64_t, uint32_t> at;
+    for (uint32_t i = 0; i < n; ++i) {
+      const uint32_t vp = vp_of(backends[i]);
+      const auto it = at.find(svc_id(backends[i].vaddr, vp));
+      uint32_t k;
+      if (it != at.end()) {
+        k = it->second;
+      } else {
+        if (lb->list->svcs.size() == XSKNF_GPU_LB_MAX_SERVICES) {
+          free_lb(lb);
+          return -EINVAL;
+        }
+        k = static_cast<uint32_t>(lb->list->svcs.size());
+        at.emplace(svc_id(backends[i].vaddr, vp), k);
+        lb->list->svcs.push_back(xsknf_gpu_lb_list::Svc{backends[i].vaddr, vp, {}});
       }
-      lb->svc[s].vaddr = r.vaddr;
-      lb->svc[s].vp = vp;
-      order[lb->services++] = s;
+      lb->list->svcs[k].bk.push_back(backend_of_record(backends[i]));
     }
-    ++lb->svc[s].count;
+  } catch (const std::bad_alloc &) {
+    free_lb(lb);
+    return -ENOMEM;
   }
-  // each service's first backend; then pass 2 places the records (count is
-  // rebuilt as the fill level)
-  uint32_t first = 0;
-  for (uint32_t k = 0; k < lb->services; ++k) {
-    Service &e = lb->svc[order[k]];
-    e.first = first;
-    first += e.count;
-    e.count = 0;
+  if (!build_tables(*lb->list, lb->svc_slots, &lb->svc, &lb->bk)) {
+    free_lb(lb);
+    return -ENOMEM;
   }
-  free(order);
-  for (uint32_t i = 0; i < n; ++i) {
-    const xsknf_gpu_lb_backend &r = backends[i];
-    const uint32_t vp = static_cast<uint32_t>(r.vport) | static_cast<uint32_t>(r.proto) << 16;
-    // (probe by the key alone: every service is stored, and vp != 0 is no empty slot's)
-    uint32_t s = xsknf_gpu::acl_hash(r.vaddr, vp, 0, 0) & smask;
-    while (!(lb->svc[s].vaddr == r.vaddr && lb->svc[s].vp == vp)) s = (s + 1) & smask;
-    Service &e = lb->svc[s];
-    lb->bk[e.first + e.count++] = Backend{r.addr, static_cast<uint32_t>(r.port) | static_cast<uint32_t>(r.ifindex) << 16,
-                                          mac_lo(r.mac), mac_hi(r.mac)};
-  }
+  lb->services = static_cast<uint32_t>(lb->list->svcs.size());
 #ifndef XSKNF_LB_HOST_ONLY
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
@@ -270,6 +406,7 @@ int xsknf_gpu_lb_create(struct xsknf_gpu_lb **lb_out, const struct xsknf_gpu_lb_
     free_lb(lb);
     return rc;
   }
+  lb->d_base = d;
   lb->d_svc = reinterpret_cast<Service *>(p);
   lb->d_bk = reinterpret_cast<Backend *>(p + sb);
   lb->d_keys = reinterpret_cast<Key *>(p + sb + bb);
@@ -305,8 +442,10 @@ int xsknf_gpu_lb_destroy(struct xsknf_gpu_lb *lb) {
   int rc = 0;
 #ifndef XSKNF_LB_HOST_ONLY
   if (lb->d_svc) {
-    rc = xsknf_gpu::lb_remove_release(lb);
-    const hipError_t e = hipFree(lb->d_svc);
+    rc = xsknf_gpu::lb_backends_release(lb);
+    const int rrc = xsknf_gpu::lb_remove_release(lb);
+    if (rrc) rc = rrc;
+    const hipError_t e = hipFree(lb->d_base);
     if (e != hipSuccess) rc = hip_rc(e, "load balancer release");
   }
 #endif
@@ -454,6 +593,160 @@ int xsknf_gpu_lb_sessions_dump(const struct xsknf_gpu_lb *lb, int which, struct 
   free(tmp);
   return rc;
 #else
+  return -ENODEV;
+#endif
+}
+
+int xsknf_gpu_lb_backends_update(struct xsknf_gpu_lb *lb, const struct xsknf_gpu_lb_backend_op *ops, uint32_t n,
+                                 void *stream) {
+  if (!lb || (n && !ops)) return -EINVAL;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (ops[i].op != XSKNF_GPU_LB_BACKEND_ADD && ops[i].op != XSKNF_GPU_LB_BACKEND_REMOVE) return -EINVAL;
+    if (ops[i].backend.proto != 6 && ops[i].backend.proto != 17) return -EINVAL;
+  }
+  if (n == 0) return 0;
+  // Everything that can fail for want of room or memory happens on copies; the
+  // object changes only behind the line "commit".
+  std::unique_ptr<xsknf_gpu_lb_list> work;
+  Service *svc = nullptr;
+  Backend *bk = nullptr;
+  uint32_t total = 0;
+  try {
+    work.reset(new xsknf_gpu_lb_list(*lb->list));
+    edit_list(*work, ops, n);
+    size_t t = 0;
+    for (const auto &s : work->svcs) t += s.bk.size();
+    if (t > XSKNF_GPU_LB_MAX_BACKENDS || work->svcs.size() > XSKNF_GPU_LB_MAX_SERVICES) return -ENOSPC;
+    total = static_cast<uint32_t>(t);
+  } catch (const std::bad_alloc &) {
+    return -ENOMEM;
+  }
+  if (!build_tables(*work, lb->svc_slots, &svc, &bk)) return -ENOMEM;
+#ifndef XSKNF_LB_HOST_ONLY
+  xsknf_gpu::LbStage *stage = nullptr;
+  uint32_t entries = 0;
+  if (lb->d_svc) {
+    // What the device copy lacks: the slots and entries that differ from the
+    // host copy it mirrors -- or everything, where it has to move to the region
+    // of the first update, or where the entries would be no shorter (32 bytes
+    // each against 16 of the table).
+    const bool first = static_cast<void *>(lb->d_svc) != lb->d_region || !lb->d_region;
+    const uint32_t all = lb->svc_slots + total;
+    uint32_t changed = 0;
+    for (uint32_t s = 0; s < lb->svc_slots; ++s) changed += memcmp(&svc[s], &lb->svc[s], sizeof(Service)) != 0;
+    for (uint32_t i = 0; i < total; ++i)
+      changed += i >= lb->backends || memcmp(&bk[i], &lb->bk[i], sizeof(Backend)) != 0;
+    const bool whole = first || 2 * static_cast<uint64_t>(changed) >= all;
+    if (whole || changed) {
+      void *host = nullptr;
+      const size_t bytes = whole ? sizeof(Backend) * static_cast<size_t>(all) : sizeof(xsknf_gpu::LbEntry) * changed;
+      const int rc = xsknf_gpu::lb_backends_prepare(lb, bytes, &stage, &host);
+      if (rc) {
+        free(svc);
+        free(bk);
+        return rc;
+      }
+      if (whole) {
+        memcpy(host, svc, sizeof(Service) * lb->svc_slots);
+        memcpy(static_cast<char *>(host) + sizeof(Service) * lb->svc_slots, bk, sizeof(Backend) * total);
+      } else {
+        xsknf_gpu::LbEntry *e = static_cast<xsknf_gpu::LbEntry *>(host);
+        for (uint32_t s = 0; s < lb->svc_slots; ++s)
+          if (memcmp(&svc[s], &lb->svc[s], sizeof(Service))) {
+            *e = xsknf_gpu::LbEntry{s, {0, 0, 0}, {svc[s].vaddr, svc[s].vp, svc[s].first, svc[s].count}};
+            ++e;
+          }
+        for (uint32_t i = 0; i < total; ++i)
+          if (i >= lb->backends || memcmp(&bk[i], &lb->bk[i], sizeof(Backend))) {
+            *e = xsknf_gpu::LbEntry{lb->svc_slots + i, {0, 0, 0}, {bk[i].addr, bk[i].pi, bk[i].m0, bk[i].m1}};
+            ++e;
+          }
+        entries = changed;
+      }
+    }
+  }
+#endif
+  // commit
+  free(lb->svc);
+  free(lb->bk);
+  delete lb->list;
+  lb->svc = svc;
+  lb->bk = bk;
+  lb->list = work.release();
+  lb->services = static_cast<uint32_t>(lb->list->svcs.size());
+  lb->backends = total;
+#ifndef XSKNF_LB_HOST_ONLY
+  if (stage) return xsknf_gpu::lb_backends_enqueue(lb, stage, entries, stream);
+#else
+  (void)stream;
+#endif
+  return 0;
+}
+
+int xsknf_gpu_lb_backends_dump(const struct xsknf_gpu_lb *lb, int which, struct xsknf_gpu_lb_backend *records,
+                               uint32_t cap, uint32_t *n_out) {
+  if (!lb || !n_out || (cap && !records)) return -EINVAL;
+  if (which == XSKNF_GPU_LB_HOST_TABLE)
+    return dump_services(lb->svc, lb->svc_slots, lb->bk, lb->backends, records, cap, n_out);
+  if (which != XSKNF_GPU_LB_DEVICE_TABLE) return -EINVAL;
+  if (!lb->d_svc) return -ENODEV;
+#ifndef XSKNF_LB_HOST_ONLY
+  const size_t sb = sizeof(Service) * lb->svc_slots, bb = sizeof(Backend) * static_cast<size_t>(lb->backends);
+  char *tmp = static_cast<char *>(malloc(sb + bb + 1));
+  if (!tmp) return -ENOMEM;
+  hipError_t e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(tmp, lb->d_svc, sb, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && bb) e = hipMemcpy(tmp + sb, lb->d_bk, bb, hipMemcpyDeviceToHost);
+  const int rc = e == hipSuccess ? dump_services(reinterpret_cast<Service *>(tmp), lb->svc_slots,
+                                                 reinterpret_cast<Backend *>(tmp + sb), lb->backends, records, cap, n_out)
+                                 : hip_rc(e, "load balancer backends_dump");
+  free(tmp);
+  return rc;
+#else
+  return -ENODEV;
+#endif
+}
+
+int xsknf_gpu_lb_drain_backends_host(struct xsknf_gpu_lb *lb, const struct xsknf_gpu_lb_backend_id *list, uint32_t n,
+                                     uint64_t *result) {
+  int rc = drain_list_args(lb, list, n);
+  if (rc) return rc;
+  report(result, 0, 0);
+  if (n == 0) return 0;
+  std::vector<IdSlot> set;
+  try {
+    id_set_of(list, n, set);
+  } catch (const std::bad_alloc &) {
+    return -ENOMEM;
+  }
+  rc = want_scratch(lb);
+  if (rc) return rc;
+  uint64_t removed = 0;
+  for (uint32_t s = 0; s < lb->slots; ++s)
+    if (live(lb->keys[s]) && id_listed(set.data(), static_cast<uint32_t>(set.size()), drain_candidate(lb->keys[s], lb->vals[s]))) {
+      bury(lb, s);
+      ++removed;
+    }
+  report(result, removed, settle(lb));
+  return 0;
+}
+
+int xsknf_gpu_lb_drain_backends(struct xsknf_gpu_lb *lb, const struct xsknf_gpu_lb_backend_id *list, uint32_t n,
+                                uint64_t *result_dev, void *stream) {
+  const int rc = drain_list_args(lb, list, n);
+  if (rc) return rc;
+  if (reinterpret_cast<uintptr_t>(result_dev) & 7) return -EINVAL;
+  if (!lb->d_svc) return -ENODEV;
+#ifndef XSKNF_LB_HOST_ONLY
+  std::vector<IdSlot> set;
+  try {
+    if (n) id_set_of(list, n, set);
+  } catch (const std::bad_alloc &) {
+    return -ENOMEM;
+  }
+  return xsknf_gpu::lb_drain_list_enqueue(lb, set.data(), static_cast<uint32_t>(set.size()), result_dev, stream);
+#else
+  (void)stream;
   return -ENODEV;
 #endif
 }

@@ -1,7 +1,8 @@
 // lb_remove_device.hip -- removing sessions from the load balancer's device table
 // (include/xsknf_gpu.h xsknf_gpu_lb_sessions_remove, _drain_backend,
-// _sessions_clear; lb.cpp validates and calls the functions below, which
-// lb_table.h declares; the kernels are kernel_lb_remove.h's).
+// _drain_backends, _sessions_clear; lb.cpp validates and calls the functions
+// below, which lb_table.h declares; the kernels are kernel_lb_remove.h's and
+// kernel_lb_drain_list.h's).
 //
 // Everything is enqueued on the caller's stream and nothing is read back:
 //   remove  [result zeroed] one async copy of the key list, 16 B per key, from a
@@ -9,6 +10,8 @@
 //           compaction launches, which return at once unless the tombstones
 //           have passed the bound
 //   drain   [result zeroed] lb_drain over the slots and the same four launches
+//   drain a list  [result zeroed] one async copy of the listed backends as a set,
+//           8 B per slot, lb_drain_list over the slots and the same four launches
 //   clear   one memset over the keys, the values and the two counters
 //
 // The caller's key list is host memory that the call must not reference after it
@@ -31,19 +34,9 @@
 #include <vector>
 
 #include "checksummer_internal.h"
+#include "kernel_lb_drain_list.h"
 #include "kernel_lb_remove.h"
-
-namespace xsknf_gpu {
-
-struct LbStage {
-  void *host;      // pinned, cap bytes
-  void *dev;       // cap bytes
-  size_t cap;
-  hipEvent_t done;
-  bool recorded;   // `done` lies on a stream
-};
-
-}  // namespace xsknf_gpu
+#include "lb_stage.h"
 
 struct xsknf_gpu_lb_staging {
   std::vector<xsknf_gpu::LbStage *> stages;
@@ -72,8 +65,10 @@ int stage_free(LbStage *st) {
   return rc;
 }
 
+}  // namespace
+
 // The smallest stage of at least `bytes` bytes that its stream has passed, or a new one.
-int stage_acquire(xsknf_gpu_lb *lb, size_t bytes, LbStage **out) {
+int lb_stage_acquire(xsknf_gpu_lb *lb, size_t bytes, LbStage **out) {
   if (!lb->staging && !(lb->staging = new (std::nothrow) xsknf_gpu_lb_staging())) return -ENOMEM;
   LbStage *best = nullptr;
   for (LbStage *st : lb->staging->stages) {
@@ -127,6 +122,8 @@ int stage_acquire(xsknf_gpu_lb *lb, size_t bytes, LbStage **out) {
   return 0;
 }
 
+namespace {
+
 int want_spare(xsknf_gpu_lb *lb) {
   if (lb->d_spare) return 0;
   const size_t bytes = (sizeof(lb::Key) + sizeof(lb::Val)) * static_cast<size_t>(lb->slots);
@@ -173,7 +170,7 @@ int lb_remove_enqueue(xsknf_gpu_lb *lb, const void *keys, uint32_t n, bool pair,
   const size_t bytes = sizeof(struct xsknf_gpu_lb_session_key) * static_cast<size_t>(n);
   if (n) {
     int rc = want_spare(lb);
-    if (!rc) rc = stage_acquire(lb, bytes, &st);
+    if (!rc) rc = lb_stage_acquire(lb, bytes, &st);
     if (rc) return rc;
   }
   hipError_t e = result_dev ? hipMemsetAsync(result_dev, 0, sizeof(uint64_t) * XSKNF_GPU_LB_REMOVE_RESULT, s) : hipSuccess;
@@ -209,6 +206,34 @@ int lb_drain_enqueue(xsknf_gpu_lb *lb, uint32_t addr, uint32_t port, uint32_t pr
   enqueue_compaction(a, s);
   e = hipGetLastError();
   if (e != hipSuccess) return hip_rc(e, "load balancer drain");
+  return 0;
+}
+
+int lb_drain_list_enqueue(xsknf_gpu_lb *lb, const void *set, uint32_t set_slots, uint64_t *result_dev, void *stream) {
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  LbStage *st = nullptr;
+  const size_t bytes = sizeof(lb::IdSlot) * static_cast<size_t>(set_slots);
+  if (set_slots) {
+    int rc = want_spare(lb);
+    if (!rc) rc = lb_stage_acquire(lb, bytes, &st);
+    if (rc) return rc;
+  }
+  hipError_t e = result_dev ? hipMemsetAsync(result_dev, 0, sizeof(uint64_t) * XSKNF_GPU_LB_REMOVE_RESULT, s) : hipSuccess;
+  if (e != hipSuccess) return hip_rc(e, "load balancer list drain");
+  if (set_slots == 0) return 0;
+  memcpy(st->host, set, bytes);
+  e = hipMemcpyAsync(st->dev, st->host, bytes, hipMemcpyHostToDevice, s);
+  if (e != hipSuccess) return hip_rc(e, "load balancer list drain copy");
+  lbr::ListArgs a;
+  a.t = table_args(lb, result_dev);
+  a.set = static_cast<const lb::IdSlot *>(st->dev);
+  a.set_slots = set_slots;
+  hipLaunchKernelGGL(lbr::lb_drain_list, grid_for(a.t.slots), dim3(lbr::kThreads), 0, s, a);
+  enqueue_compaction(a.t, s);
+  e = hipGetLastError();
+  if (e == hipSuccess) e = hipEventRecord(st->done, s);
+  st->recorded = true;   // (also after an error: the copy may be under way)
+  if (e != hipSuccess) return hip_rc(e, "load balancer list drain");
   return 0;
 }
 

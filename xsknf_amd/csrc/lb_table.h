@@ -27,7 +27,8 @@
 // thus never pass 3/4 of the slots: every probe sequence keeps an empty slot.
 // The services are a table of the same kind, {vaddr, vport | proto << 16} ->
 // {first, count}: the service's backends are bk[first .. first + count) in the
-// order their records were given.
+// order their records were given.  It has no tombstone: an update rebuilds it
+// (lb.cpp), so a probe that ends at count == 0 has seen every service.
 #pragma once
 #include <stdint.h>
 
@@ -133,6 +134,30 @@ XSKNF_HD inline bool is_partner(const Key &pk, const Val &pv, const Key &k, cons
 XSKNF_HD inline bool drains(const Key &k, const Val &v, uint32_t addr, uint32_t port, uint32_t proto) {
   if (k.p != proto) return false;
   return dir_of(v) == kToBackend ? v.addr == addr && (v.pi & 0xffff) == port : k.a == addr && (k.c & 0xffff) == port;
+}
+
+// drain_backends' form of the same predicate.  A live slot names one backend,
+// the one `drains` compares with: {addr, port | proto << 16}, the value's for a
+// TO_BACKEND session, the key's source for a TO_CLIENT one.  The list is an
+// open-addressing set of such pairs (lb.cpp builds it: a power of two, at most
+// half full, linear probing from acl_hash(addr, pw, 0, 0); pw == 0 is an empty
+// slot, which no backend's is: its proto is 6 or 17).
+struct IdSlot {
+  uint32_t addr, pw;
+};
+XSKNF_HD inline IdSlot drain_candidate(const Key &k, const Val &v) {
+  return dir_of(v) == kToBackend ? IdSlot{v.addr, (v.pi & 0xffff) | k.p << 16} : IdSlot{k.a, (k.c & 0xffff) | k.p << 16};
+}
+XSKNF_HD inline bool id_listed(const IdSlot *set, uint32_t set_slots, const IdSlot &c) {
+  const uint32_t mask = set_slots - 1;
+  uint32_t s = acl_hash(c.addr, c.pw, 0, 0) & mask;
+  for (uint32_t i = 0; i < set_slots; ++i) {   // bounded whatever the set holds
+    const IdSlot e = set[s];
+    if (e.pw == 0) return false;
+    if (e.addr == c.addr && e.pw == c.pw) return true;
+    s = (s + 1) & mask;
+  }
+  return false;
 }
 
 // The service {vaddr, vport, proto}, or NULL.
@@ -345,30 +370,43 @@ XSKNF_HD inline int32_t frame(const Tables &t, const Gate &gate, uint8_t *f, uin
 }  // namespace lb
 }  // namespace xsknf_gpu
 
-// The object behind struct xsknf_gpu_lb: the services and backends (immutable
-// after creation) and a session table on the host and, unless built with
-// XSKNF_LB_HOST_ONLY (the sanitizer program, tests/c/san_lb.c), on the device
-// current at creation.  The two session tables are independent: the host call
-// works on one, the device call on the other.
+// The object behind struct xsknf_gpu_lb: the services and backends and a session
+// table on the host and, unless built with XSKNF_LB_HOST_ONLY (the sanitizer
+// programs, tests/c/san_lb.c), on the device current at creation.  The two
+// session tables are independent: the host call works on one, the device call
+// on the other.  The services and backends change through
+// xsknf_gpu_lb_backends_update (lb.cpp): `list` is the ordered record list the
+// object stands for, svc / bk are rebuilt from it by every update (the builder
+// _create uses), and the device copy follows in stream order
+// (lb_backends_device.hip).
+struct xsknf_gpu_lb_list;              // lb.cpp: the services in the order they came to be, each with its backends
 struct xsknf_gpu_lb {
   uint32_t slots, max_sessions, svc_slots, services, backends;
-  xsknf_gpu::lb::Service *svc;
-  xsknf_gpu::lb::Backend *bk;
+  xsknf_gpu::lb::Service *svc;         // svc_slots slots; replaced by an update
+  xsknf_gpu::lb::Backend *bk;          // `backends` entries, service after service; replaced by an update
+  xsknf_gpu_lb_list *list;
   xsknf_gpu::lb::Key *keys;
   xsknf_gpu::lb::Val *vals;
   uint32_t count;
   uint32_t tombstones;                 // host table: slots that hold kTombstoneP
   xsknf_gpu::lb::Key *live_k;          // host: room for max_sessions sessions while the table is rebuilt
   xsknf_gpu::lb::Val *live_v;          //   (NULL until the first host removal)
-  // device (all NULL in a host-only object): one allocation, d_svc first
+  // device (all NULL in a host-only object): d_base is creation's one
+  // allocation -- services, backends, keys, values, counters.  d_svc / d_bk
+  // point into it until the first update, then into d_region
+  void *d_base;
   xsknf_gpu::lb::Service *d_svc;
   xsknf_gpu::lb::Backend *d_bk;
   xsknf_gpu::lb::Key *d_keys;
   xsknf_gpu::lb::Val *d_vals;
   uint32_t *d_count;                   // d_count[1]: the device table's tombstones
   uint64_t device_bytes;
+  // lb_backends_device.hip (NULL until the first update): svc_slots service
+  // slots and XSKNF_GPU_LB_MAX_BACKENDS backends, one array of 16-byte entries
+  void *d_region;
   // lb_remove_device.hip (NULL until the first device removal): the spare table
-  // a compaction rebuilds into, keys then values, and the key lists' buffers
+  // a compaction rebuilds into, keys then values; and the pinned buffers of the
+  // calls in flight (removals, list drains, updates)
   xsknf_gpu::lb::Key *d_spare;
   struct xsknf_gpu_lb_staging *staging;
 };
@@ -380,7 +418,26 @@ struct xsknf_gpu_lb {
 namespace xsknf_gpu {
 int lb_remove_enqueue(xsknf_gpu_lb *lb, const void *keys, uint32_t n, bool pair, uint64_t *result_dev, void *stream);
 int lb_drain_enqueue(xsknf_gpu_lb *lb, uint32_t addr, uint32_t port, uint32_t proto, uint64_t *result_dev, void *stream);
+// The list drain: `set` is lb.cpp's open-addressing set of set_slots entries
+// {addr, port | proto << 16} (a power of two, at most half full, second word 0:
+// empty), host memory that is copied before the call returns.
+int lb_drain_list_enqueue(xsknf_gpu_lb *lb, const void *set, uint32_t set_slots, uint64_t *result_dev, void *stream);
 int lb_clear_enqueue(xsknf_gpu_lb *lb, void *stream);
 int lb_remove_release(xsknf_gpu_lb *lb);   // _destroy
+
+// lb_backends_device.hip: an update's way to the device copy.  _prepare makes
+// sure of the region and of a pinned buffer of `bytes` bytes (*host_out), and
+// changes nothing else; after it lb.cpp fills the buffer and commits the host
+// copy, and _enqueue cannot fail for want of memory.  entries > 0: the buffer
+// holds that many LbEntry, scattered by one launch; entries == 0: it holds the
+// table whole, svc_slots + lb->backends 16-byte entries, copied over the region.
+struct LbStage;
+struct LbEntry {
+  uint32_t index, pad[3];   // below svc_slots: a service slot; from there: backend index - svc_slots
+  uint32_t w[4];            // the Service or the Backend
+};
+int lb_backends_prepare(xsknf_gpu_lb *lb, size_t bytes, LbStage **stage_out, void **host_out);
+int lb_backends_enqueue(xsknf_gpu_lb *lb, LbStage *stage, uint32_t entries, void *stream);
+int lb_backends_release(xsknf_gpu_lb *lb);   // _destroy, before lb_remove_release
 }  // namespace xsknf_gpu
 #endif

@@ -16,7 +16,10 @@ the model the device is held to).  Both rewrite the UMEM in place; the verdicts
 are what route.route_batch consumes.  Sessions end through
 `LoadBalancer.sessions_remove`, `drain_backend` and `sessions_clear`
 (xsknf_amd/csrc/lb_remove_device.hip for the device table): on the device they
-are enqueued between batches and wait for nothing.
+are enqueued between batches and wait for nothing.  The services and backends
+change under traffic through `LoadBalancer.backends_update`
+(xsknf_amd/csrc/lb_backends_device.hip for the device copy), and
+`drain_backends` ends the flows of a list of backends in one pass.
 """
 from __future__ import annotations
 
@@ -46,7 +49,13 @@ KEY_DTYPE = np.dtype([("saddr", "<u4"), ("daddr", "<u4"), ("sport", "<u2"), ("dp
                       ("pad", "u1", (3,))])
 VALUE_DTYPE = np.dtype([("addr", "<u4"), ("port", "<u2"), ("ifindex", "<u2"), ("mac", "u1", (6,)), ("dir", "u1"),
                         ("pad", "u1")])
+# struct xsknf_gpu_lb_backend_op: a backend record and BACKEND_ADD or BACKEND_REMOVE
+BACKEND_ADD, BACKEND_REMOVE = _lib.LB_BACKEND_ADD, _lib.LB_BACKEND_REMOVE
+BACKEND_OP_DTYPE = np.dtype([("backend", BACKEND_DTYPE), ("op", "<u4")])
+# struct xsknf_gpu_lb_backend_id: what drain_backends lists
+BACKEND_ID_DTYPE = np.dtype([("addr", "<u4"), ("port", "<u2"), ("proto", "u1"), ("pad", "u1")])
 assert BACKEND_DTYPE.itemsize == 24 and KEY_DTYPE.itemsize == 16 and VALUE_DTYPE.itemsize == 16
+assert BACKEND_OP_DTYPE.itemsize == 28 and BACKEND_ID_DTYPE.itemsize == 8
 
 
 def _records(a, itemsize: int, what: str) -> np.ndarray:
@@ -62,6 +71,7 @@ class LoadBalancer:
 
     def __init__(self, handle: int):
         self._h = handle
+        self._device_half = None   # whether the object has a device half (asked once)
 
     @classmethod
     def from_backends(cls, backends, max_sessions: int = MAX_SESSIONS, slots: int = 0, *, device=None) -> "LoadBalancer":
@@ -82,7 +92,9 @@ class LoadBalancer:
             import torch
             with torch.cuda.device(device):
                 create()
-        return cls(h.value)
+        made = cls(h.value)
+        made._has_device_half()   # (asked now: _info waits for the device, which a later update must not)
+        return made
 
     @property
     def handle(self) -> int:
@@ -170,6 +182,77 @@ class LoadBalancer:
         res, s = self._device_result(stream)
         _lib.check(_lib.load().xsknf_gpu_lb_drain_backend(self.handle, addr, port, proto, res.data_ptr(),
                                                           ctypes.c_void_p(s or None)), "xsknf_gpu_lb_drain_backend")
+        return res
+
+    def _has_device_half(self) -> bool:
+        if self._device_half is None:
+            self._device_half = self.info["device_bytes"] != 0
+        return self._device_half
+
+    def backends_update(self, add=None, remove=None, *, ops=None, stream=None) -> None:
+        """xsknf_gpu_lb_backends_update: edit the services and backends of the
+        live object.  Either `ops`, BACKEND_OP_DTYPE records applied in order,
+        or BACKEND_DTYPE records to `remove` and to `add`, the removals first.
+        The host copy is new when the call returns; the device copy follows on
+        `stream` (default: the current stream of the current device, which
+        must be the object's), and nothing waits for it.  A host-only object
+        ignores `stream`."""
+        if ops is not None:
+            if add is not None or remove is not None:
+                raise ValueError("give ops, or add and remove, not both")
+            o = _records(ops, 28, "ops")
+        else:
+            parts = []
+            for recs, op in ((remove, BACKEND_REMOVE), (add, BACKEND_ADD)):
+                if recs is None:
+                    continue
+                r = _records(recs, 24, "backends")
+                part = np.zeros(r.size, dtype=BACKEND_OP_DTYPE)
+                part["backend"] = r.view(BACKEND_DTYPE)
+                part["op"] = op
+                parts.append(part)
+            o = np.concatenate(parts) if parts else np.zeros(0, dtype=BACKEND_OP_DTYPE)
+        s = 0
+        if o.size and self._has_device_half():
+            import torch
+
+            s = int(getattr(stream, "cuda_stream", stream)) if stream is not None else torch.cuda.current_stream().cuda_stream
+        _lib.check(_lib.load().xsknf_gpu_lb_backends_update(self.handle, o.ctypes.data if o.size else None, o.size,
+                                                            ctypes.c_void_p(s or None)), "xsknf_gpu_lb_backends_update")
+
+    def backends_dump(self, which: int = HOST_TABLE) -> np.ndarray:
+        """xsknf_gpu_lb_backends_dump: the BACKEND_DTYPE records of the host or
+        the device copy, services ascending, a service's backends by number.
+        The device form waits for the device."""
+        lib = _lib.load()
+        n = ctypes.c_uint32(0)
+        rc = lib.xsknf_gpu_lb_backends_dump(self.handle, which, None, 0, ctypes.byref(n))
+        if rc not in (0, -errno.ENOSPC):
+            _lib.check(rc, "xsknf_gpu_lb_backends_dump")
+        r = np.zeros(int(n.value), dtype=BACKEND_DTYPE)
+        if r.size:
+            _lib.check(lib.xsknf_gpu_lb_backends_dump(self.handle, which, r.ctypes.data, r.size, ctypes.byref(n)),
+                       "xsknf_gpu_lb_backends_dump")
+        return r
+
+    def drain_backends(self, ids, *, which: int = DEVICE_TABLE, stream=None):
+        """xsknf_gpu_lb_drain_backends / _drain_backends_host: both halves of
+        every flow of every listed backend (BACKEND_ID_DTYPE records) leave one
+        session table, in one pass over it.  Returns the result words as
+        `drain_backend` does.  To take backends out of service, call
+        `backends_update(remove=...)` first and this on the same stream."""
+        i = _records(ids, 8, "ids")
+        ip = i.ctypes.data if i.size else None
+        if which == HOST_TABLE:
+            res = np.zeros(_lib.LB_REMOVE_RESULT, dtype=np.uint64)
+            _lib.check(_lib.load().xsknf_gpu_lb_drain_backends_host(self.handle, ip, i.size, res.ctypes.data),
+                       "xsknf_gpu_lb_drain_backends_host")
+            return res
+        if which != DEVICE_TABLE:
+            raise ValueError("which must be HOST_TABLE or DEVICE_TABLE")
+        res, s = self._device_result(stream)
+        _lib.check(_lib.load().xsknf_gpu_lb_drain_backends(self.handle, ip, i.size, res.data_ptr(),
+                                                           ctypes.c_void_p(s or None)), "xsknf_gpu_lb_drain_backends")
         return res
 
     def sessions_clear(self, which: int, *, stream=None) -> None:
