@@ -830,6 +830,12 @@ XSKNF_GPU_API int xsknf_gpu_firewall_host(const uint8_t *umem, uint64_t umem_siz
  *      old check and the old port taken after promotion to 32 bits.  For ihl < 5
  *      these fields overlap and the order of the reads and writes shows.
  *      The verdict is rep.ifindex (0..65535).
+ *  11. with ageing enabled (xsknf_gpu_lb_aging_enable below): a frame that takes
+ *      its session from the table (rule 7) stamps that session with the table's
+ *      clock, and rule 9 stamps every session it stores with it, the forward
+ *      one and the backward one whether new or replacing.  A failed insert
+ *      stamps nothing, and neither does a frame that passes, is dropped, lies
+ *      outside the UMEM or is decided by the lbfw NF's ACL (rule 6a).
  * Multi-byte values are the frame's bytes read little-endian, as the reference
  * reads them on the hosts it runs on.
  *
@@ -994,6 +1000,67 @@ XSKNF_GPU_API int xsknf_gpu_lb_drain_backend(struct xsknf_gpu_lb *lb, uint32_t a
 XSKNF_GPU_API int xsknf_gpu_lb_drain_backend_host(struct xsknf_gpu_lb *lb, uint32_t addr, uint16_t port,
 		uint8_t proto, uint64_t *result);
 XSKNF_GPU_API int xsknf_gpu_lb_sessions_clear(struct xsknf_gpu_lb *lb, int which, void *stream);
+
+/* Ageing: ending the flows that have been idle too long.  The reference leaves
+ * this out ("This map should be handled in a LRU way ... This is not done for
+ * simplicity", load_balancer_user.c:51-56); without it a table that has reached
+ * max_sessions fails every new flow's insert until the caller names sessions to
+ * remove, which it cannot: the batches create them on the device.  Ageing is
+ * opt-in per object, and an object that never enables it behaves, allocates and
+ * launches exactly as before.
+ *
+ * _aging_enable: call it with no batch in flight (it may wait for the device).
+ * Each session table gets one uint32_t last-seen stamp per slot, a side array --
+ * the slots' layout stays -- and a clock word.  Both clocks start at 0 and every
+ * session already stored is stamped with its table's clock.  Idempotent.  The
+ * device table's stamps and clock, 4 B per slot (64 MiB at
+ * XSKNF_GPU_LB_MAX_SLOTS) and 16 B, are part of device_bytes; the spare table of
+ * the removals gets stamps of the same size with its own allocation, or here
+ * if it already exists.  From then on rule 11 holds for xsknf_gpu_lb_batch,
+ * xsknf_gpu_lbfw_batch and their _host forms, _sessions_put stamps each
+ * session it stores or replaces with the clock of the table it stores into, and
+ * every rebuild of a table (after any removal) carries each surviving session's
+ * stamp with it.
+ *
+ * _clock: sets one table's clock to `now`, in the caller's own unit (`which` as
+ * for _sessions_dump).  The host table's clock changes at once.  The device
+ * table's changes in stream order: a batch enqueued on `stream` before the call
+ * stamps with the old value, a batch after it with the new one; the call reads
+ * nothing back and waits for nothing.  All stamps of one batch are equal.
+ *
+ * _sessions_expire (device table, on `stream`) / _sessions_expire_host: set
+ * semantics over the table as it stands when the stream reaches the call.
+ * idle(k) = (uint32_t)(clock - stamp[k]) > max_idle; the subtraction is
+ * unsigned, so a clock that wraps is handled as long as the caller keeps real
+ * idle times below 2^32 ticks (expire before a session's stamp is a full turn
+ * behind).  The checked partner of a session is REMOVE_PAIR's: the table holds
+ * the partner key, its direction is the opposite one and its own partner is
+ * this key.  A session is removed if and only if it is idle and either has no
+ * checked partner or its checked partner is idle too: both halves of a flow
+ * leave together or stay together, so a flow with traffic in one direction only
+ * keeps its backward half.  A session without a checked partner -- an unpaired
+ * _sessions_put entry, a backward session that another flow has replaced --
+ * decides alone.  The result words, the tombstones, the rebuild past slots / 4,
+ * the dropping counts, the spare table and a NULL result are the other
+ * removals'.
+ *
+ * _sessions_ages: _sessions_dump's order, cap, n_out and -ENOSPC, with ages[i] =
+ * (uint32_t)(clock - stamp) in place of the value and the table's clock in
+ * *clock_out (may be NULL).  The device table's form waits for the device.  For
+ * tests and monitoring.
+ *
+ * Everything is validated before any work.  -EINVAL: a NULL lb, an object
+ * without ageing (_clock, _sessions_expire*, _sessions_ages), a bad which, a
+ * misaligned result_dev, a NULL n_out, or NULL keys or ages with cap > 0.
+ * -ENODEV for the device table of a host-only object.  -ENOMEM.  -EIO on a HIP
+ * error (xsknf_gpu_last_error()). */
+XSKNF_GPU_API int xsknf_gpu_lb_aging_enable(struct xsknf_gpu_lb *lb);
+XSKNF_GPU_API int xsknf_gpu_lb_clock(struct xsknf_gpu_lb *lb, int which, uint32_t now, void *stream);
+XSKNF_GPU_API int xsknf_gpu_lb_sessions_expire(struct xsknf_gpu_lb *lb, uint32_t max_idle, uint64_t *result_dev,
+		void *stream);
+XSKNF_GPU_API int xsknf_gpu_lb_sessions_expire_host(struct xsknf_gpu_lb *lb, uint32_t max_idle, uint64_t *result);
+XSKNF_GPU_API int xsknf_gpu_lb_sessions_ages(const struct xsknf_gpu_lb *lb, int which,
+		struct xsknf_gpu_lb_session_key *keys, uint32_t *ages, uint32_t cap, uint32_t *n_out, uint32_t *clock_out);
 
 /* The services and backends of a live object.  The object's services are the
  * ordered record list xsknf_gpu_lb_create was given; the n ops edit that list

@@ -1,0 +1,28 @@
+"""The load balancer's ageing on the host table under AddressSanitizer + UBSan, as
+a stand-alone program (tests/c/san_lb_age.c) -- CPU only, nothing preloaded."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_lb_ageing_is_sanitizer_clean(tmp_path):
+    """xsknf_amd/csrc/lb.cpp (built without its device half: XSKNF_LB_HOST_ONLY)
+    and lb_host.cpp on 300 random sequences of enable / put / batch / clock /
+    expire / remove against a model with a stamp per session, through rebuilds,
+    every buffer exactly as long as its contents."""
+    if not shutil.which("g++"):
+        pytest.skip("g++ missing")
+    exe = str(tmp_path / "san_lb_age")
+    subprocess.run(["g++", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=undefined", "-Iinclude", "-DXSKNF_LB_HOST_ONLY", "-x", "c",
+                    "tests/c/san_lb_age.c", "-x", "c++", "-std=c++17", "xsknf_amd/csrc/lb.cpp",
+                    "xsknf_amd/csrc/lb_host.cpp", "-o", exe], cwd=ROOT, check=True)
+    r = subprocess.run([exe], cwd=ROOT, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"),
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr[-4000:]
+    assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
+    assert r.stdout.strip() == "ok 300"

@@ -79,6 +79,11 @@ EXPORTED_SYMBOLS = (
     "xsknf_gpu_lb_backends_dump",
     "xsknf_gpu_lb_drain_backends",
     "xsknf_gpu_lb_drain_backends_host",
+    "xsknf_gpu_lb_aging_enable",
+    "xsknf_gpu_lb_clock",
+    "xsknf_gpu_lb_sessions_expire",
+    "xsknf_gpu_lb_sessions_expire_host",
+    "xsknf_gpu_lb_sessions_ages",
     "xsknf_gpu_lb_workspace",
     "xsknf_gpu_lb_batch",
     "xsknf_gpu_lb_host",
@@ -388,6 +393,16 @@ def load() -> ctypes.CDLL:
     lib.xsknf_gpu_lb_drain_backends.argtypes = [vp, vp, u32, vp, vp]
     lib.xsknf_gpu_lb_drain_backends_host.restype = ctypes.c_int
     lib.xsknf_gpu_lb_drain_backends_host.argtypes = [vp, vp, u32, vp]
+    lib.xsknf_gpu_lb_aging_enable.restype = ctypes.c_int
+    lib.xsknf_gpu_lb_aging_enable.argtypes = [vp]
+    lib.xsknf_gpu_lb_clock.restype = ctypes.c_int
+    lib.xsknf_gpu_lb_clock.argtypes = [vp, ctypes.c_int, u32, vp]
+    lib.xsknf_gpu_lb_sessions_expire.restype = ctypes.c_int
+    lib.xsknf_gpu_lb_sessions_expire.argtypes = [vp, u32, vp, vp]
+    lib.xsknf_gpu_lb_sessions_expire_host.restype = ctypes.c_int
+    lib.xsknf_gpu_lb_sessions_expire_host.argtypes = [vp, u32, vp]
+    lib.xsknf_gpu_lb_sessions_ages.restype = ctypes.c_int
+    lib.xsknf_gpu_lb_sessions_ages.argtypes = [vp, ctypes.c_int, vp, vp, u32, ctypes.POINTER(u32), ctypes.POINTER(u32)]
     lib.xsknf_gpu_lb_workspace.restype = ctypes.c_int
     lib.xsknf_gpu_lb_workspace.argtypes = [u32, ctypes.POINTER(u64)]
     lib.xsknf_gpu_lb_batch.restype = ctypes.c_int

@@ -27,6 +27,10 @@
 //                    compare-and-swap on p, then the other words)
 //   lb_compact_back  ... the spare table over the live one, slot by slot
 //   lb_compact_done  one lane: ... tombstones = 0, result[COMPACTED] = 1
+// With ageing (Args::stamps: include/xsknf_gpu.h xsknf_gpu_lb_aging_enable) a
+// session's last-seen stamp moves with it: lb_compact_move stores it beside the
+// slot it has claimed in the spare table, lb_compact_back copies it home.  A
+// stamp of a slot that holds no session means nothing and is never cleared.
 //
 // Why one launch gives the set semantics whatever the lane order.  A slot is
 // buried only (1) by a lane whose listed key it holds or (2) as the checked
@@ -72,6 +76,11 @@ struct Args {
   unsigned long long *result;        // 2 words, or NULL
   uint32_t n, slots, pair;
   uint32_t addr, port, proto;        // lb_drain
+  // ageing; all NULL for an object without it
+  uint32_t *stamps;                  // one per slot
+  uint32_t *spare_stamps;            // one per slot of the spare table
+  const uint32_t *clock;             // the table's clock word (lb_expire)
+  uint32_t max_idle;                 // lb_expire
 };
 
 // Bury slot s, which held a key of protocol p when the lane looked.  True for
@@ -155,6 +164,7 @@ __global__ __launch_bounds__(kThreads) void lb_compact_move(const Args a) {
         a.spare_keys[s].b = k.b;
         a.spare_keys[s].c = k.c;
         a.spare_vals[s] = v;
+        if (a.stamps) a.spare_stamps[s] = a.stamps[i];
         break;
       }
       s = (s + 1) & mask;
@@ -168,6 +178,7 @@ __global__ __launch_bounds__(kThreads) void lb_compact_back(const Args a) {
   for (uint64_t s = blockIdx.x * kThreads + threadIdx.x; s < a.slots; s += stride) {
     *reinterpret_cast<uint4 *>(a.keys + s) = *reinterpret_cast<const uint4 *>(a.spare_keys + s);
     *reinterpret_cast<uint4 *>(a.vals + s) = *reinterpret_cast<const uint4 *>(a.spare_vals + s);
+    if (a.stamps) a.stamps[s] = a.spare_stamps[s];
   }
 }
 

@@ -6,7 +6,9 @@
 // lb_remove_device.hip; and the services and backends of a live object
 // (_backends_update, _backends_dump) and the list drain (_drain_backends): the
 // ordered list is edited and the tables rebuilt here, what changed goes to
-// lb_backends_device.hip.
+// lb_backends_device.hip; and ageing (_aging_enable, _clock, _sessions_expire,
+// _sessions_ages): the stamps' allocation and the host table's expiry here, the
+// device table's in lb_remove_device.hip.
 // Plain C++; the only GPU calls are the allocation, the uploads, the table's
 // copies for _sessions_put and _sessions_dump and the release, and a build with
 // XSKNF_LB_HOST_ONLY has none (the sanitizer programs, tests/c/san_lb.c and
@@ -58,6 +60,8 @@ void free_lb(xsknf_gpu_lb *lb) {
   free(lb->vals);
   free(lb->live_k);
   free(lb->live_v);
+  free(lb->stamps);
+  free(lb->live_s);
   delete lb;
 }
 
@@ -72,9 +76,17 @@ Val val_of(const xsknf_gpu_lb_session_value &v) {
              mac_hi(v.mac) | static_cast<uint32_t>(v.dir) << 16};
 }
 
-// the sessions of a table, ascending by key
+// the host session table as a batch, _sessions_put and the removals see it
+Tables host_tables(xsknf_gpu_lb *lb) {
+  return Tables{lb->svc,       lb->bk,    lb->keys,         lb->vals,   &lb->count,
+                lb->svc_slots, lb->slots, lb->max_sessions, lb->stamps, &lb->clock};
+}
+
+// the sessions of a table, ascending by key; with `ao` (xsknf_gpu_lb_sessions_ages)
+// each one's clock - stamp in place of its value
 int dump_table(const Key *keys, const Val *vals, uint32_t slots, xsknf_gpu_lb_session_key *ko,
-               xsknf_gpu_lb_session_value *vo, uint32_t cap, uint32_t *n_out) {
+               xsknf_gpu_lb_session_value *vo, uint32_t cap, uint32_t *n_out, const uint32_t *stamps = nullptr,
+               uint32_t clock = 0, uint32_t *ao = nullptr) {
   std::vector<uint32_t> used;
   try {
     for (uint32_t s = 0; s < slots; ++s)
@@ -92,16 +104,21 @@ int dump_table(const Key *keys, const Val *vals, uint32_t slots, xsknf_gpu_lb_se
   *n_out = static_cast<uint32_t>(used.size());
   for (uint32_t i = 0; i < used.size() && i < cap; ++i) {
     const Key &k = keys[used[i]];
-    const Val &v = vals[used[i]];
     xsknf_gpu_lb_session_key kk;
-    xsknf_gpu_lb_session_value vv;
     memset(&kk, 0, sizeof(kk));
-    memset(&vv, 0, sizeof(vv));
     kk.saddr = k.a;
     kk.daddr = k.b;
     kk.sport = static_cast<uint16_t>(k.c);
     kk.dport = static_cast<uint16_t>(k.c >> 16);
     kk.proto = static_cast<uint8_t>(k.p);
+    ko[i] = kk;
+    if (ao) {
+      ao[i] = clock - stamps[used[i]];
+      continue;
+    }
+    const Val &v = vals[used[i]];
+    xsknf_gpu_lb_session_value vv;
+    memset(&vv, 0, sizeof(vv));
     vv.addr = v.addr;
     vv.port = static_cast<uint16_t>(v.pi);
     vv.ifindex = static_cast<uint16_t>(v.pi >> 16);
@@ -109,7 +126,6 @@ int dump_table(const Key *keys, const Val *vals, uint32_t slots, xsknf_gpu_lb_se
     vv.mac[4] = static_cast<uint8_t>(v.m1);
     vv.mac[5] = static_cast<uint8_t>(v.m1 >> 8);
     vv.dir = static_cast<uint8_t>(v.m1 >> 16);
-    ko[i] = kk;
     vo[i] = vv;
   }
   return used.size() > cap ? -ENOSPC : 0;
@@ -132,18 +148,23 @@ constexpr uint32_t kRemoveFlags = XSKNF_GPU_LB_REMOVE_PAIR;
 
 // The scratch of a rebuild, made by the first removal so that none can fail
 // half way: count <= max_sessions always (put and the kernels refuse beyond it).
+// With ageing the stamps have their room too (_aging_enable adds it where the
+// scratch already exists).
 int want_scratch(xsknf_gpu_lb *lb) {
   if (lb->live_k) return 0;
   const size_t room = lb->max_sessions ? lb->max_sessions : 1;
   Key *k = static_cast<Key *>(malloc(sizeof(Key) * room));
   Val *v = static_cast<Val *>(malloc(sizeof(Val) * room));
-  if (!k || !v) {
+  uint32_t *st = lb->stamps ? static_cast<uint32_t *>(malloc(sizeof(uint32_t) * room)) : nullptr;
+  if (!k || !v || (lb->stamps && !st)) {
     free(k);
     free(v);
+    free(st);
     return -ENOMEM;
   }
   lb->live_k = k;
   lb->live_v = v;
+  lb->live_s = st;
   return 0;
 }
 
@@ -161,6 +182,7 @@ uint64_t settle(xsknf_gpu_lb *lb) {
   for (uint32_t s = 0; s < lb->slots; ++s)
     if (live(lb->keys[s])) {
       lb->live_k[n] = lb->keys[s];
+      if (lb->stamps) lb->live_s[n] = lb->stamps[s];   // a session's stamp moves with it
       lb->live_v[n++] = lb->vals[s];
     }
   memset(lb->keys, 0, sizeof(Key) * lb->slots);
@@ -171,6 +193,7 @@ uint64_t settle(xsknf_gpu_lb *lb) {
     while (lb->keys[s].p) s = (s + 1) & mask;   // (the keys are distinct and at most half the slots)
     lb->keys[s] = lb->live_k[i];
     lb->vals[s] = lb->live_v[i];
+    if (lb->stamps) lb->stamps[s] = lb->live_s[i];
   }
   lb->tombstones = 0;
   return 1;
@@ -445,7 +468,9 @@ int xsknf_gpu_lb_destroy(struct xsknf_gpu_lb *lb) {
     rc = xsknf_gpu::lb_backends_release(lb);
     const int rrc = xsknf_gpu::lb_remove_release(lb);
     if (rrc) rc = rrc;
-    const hipError_t e = hipFree(lb->d_base);
+    hipError_t e = hipFree(lb->d_base);
+    if (e != hipSuccess) rc = hip_rc(e, "load balancer release");
+    e = lb->d_stamps ? hipFree(lb->d_stamps) : hipSuccess;
     if (e != hipSuccess) rc = hip_rc(e, "load balancer release");
   }
 #endif
@@ -550,23 +575,27 @@ int xsknf_gpu_lb_sessions_put(struct xsknf_gpu_lb *lb, const struct xsknf_gpu_lb
     if (keys[i].proto != 6 && keys[i].proto != 17) return -EINVAL;
   }
   if (n == 0) return 0;
-  int rc = put_all(Tables{lb->svc, lb->bk, lb->keys, lb->vals, &lb->count, lb->svc_slots, lb->slots, lb->max_sessions},
-                   keys, values, n);
+  int rc = put_all(host_tables(lb), keys, values, n);
 #ifndef XSKNF_LB_HOST_ONLY
   if (lb->d_svc) {
-    // the device table through a host copy: the same insert, the same order
+    // the device table through a host copy: the same insert, the same order; with
+    // ageing its stamps and its clock word (d_stamps' allocation) make the same trip
     const size_t kb = sizeof(Key) * static_cast<size_t>(lb->slots), vb = sizeof(Val) * static_cast<size_t>(lb->slots);
-    char *tmp = static_cast<char *>(malloc(kb + vb + 16));
+    const size_t sb = lb->d_stamps ? sizeof(uint32_t) * (static_cast<size_t>(lb->slots) + 1) : 0;
+    char *tmp = static_cast<char *>(malloc(kb + vb + 16 + sb));
     if (!tmp) return -ENOMEM;
+    uint32_t *st = sb ? reinterpret_cast<uint32_t *>(tmp + kb + vb + 16) : nullptr;
     hipError_t e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(tmp, lb->d_keys, kb + vb + 16, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && sb) e = hipMemcpy(st, lb->d_stamps, sb, hipMemcpyDeviceToHost);
     if (e == hipSuccess) {
       const int drc = put_all(Tables{lb->svc, lb->bk, reinterpret_cast<Key *>(tmp), reinterpret_cast<Val *>(tmp + kb),
                                      reinterpret_cast<uint32_t *>(tmp + kb + vb), lb->svc_slots, lb->slots,
-                                     lb->max_sessions},
+                                     lb->max_sessions, st, st ? st + lb->slots : nullptr},
                               keys, values, n);
       if (!rc) rc = drc;
       e = hipMemcpy(lb->d_keys, tmp, kb + vb + 16, hipMemcpyHostToDevice);
+      if (e == hipSuccess && sb) e = hipMemcpy(lb->d_stamps, st, sb - sizeof(uint32_t), hipMemcpyHostToDevice);
     }
     free(tmp);
     if (e != hipSuccess) return hip_rc(e, "load balancer sessions_put");
@@ -747,6 +776,145 @@ int xsknf_gpu_lb_drain_backends(struct xsknf_gpu_lb *lb, const struct xsknf_gpu_
   return xsknf_gpu::lb_drain_list_enqueue(lb, set.data(), static_cast<uint32_t>(set.size()), result_dev, stream);
 #else
   (void)stream;
+  return -ENODEV;
+#endif
+}
+
+// ---- ageing ---------------------------------------------------------------------------
+int xsknf_gpu_lb_aging_enable(struct xsknf_gpu_lb *lb) {
+  if (!lb) return -EINVAL;
+  if (lb->stamps) return 0;
+  // Everything is allocated before the object changes.  calloc's zeros are the
+  // stamps: every session already stored carries its table's clock, 0.
+  uint32_t *st = static_cast<uint32_t *>(calloc(lb->slots, sizeof(uint32_t)));
+  uint32_t *ls = lb->live_k ? static_cast<uint32_t *>(malloc(sizeof(uint32_t) * (lb->max_sessions ? lb->max_sessions : 1)))
+                            : nullptr;
+  if (!st || (lb->live_k && !ls)) {
+    free(st);
+    free(ls);
+    return -ENOMEM;
+  }
+#ifndef XSKNF_LB_HOST_ONLY
+  if (lb->d_svc) {
+    // the stamps and, behind them, 16 bytes whose first word is the clock
+    const size_t bytes = sizeof(uint32_t) * static_cast<size_t>(lb->slots) + 16;
+    void *d = nullptr;
+    hipError_t e = hipMalloc(&d, bytes);
+    if (e == hipSuccess) e = hipDeviceSynchronize();   // (no batch is in flight: the caller's word; a removal may be)
+    if (e == hipSuccess) e = hipMemset(d, 0, bytes);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+      const int rc = hip_rc(e, "load balancer ageing");
+      if (d) (void)hipFree(d);
+      free(st);
+      free(ls);
+      return rc;
+    }
+    lb->d_stamps = static_cast<uint32_t *>(d);
+    lb->d_clock = lb->d_stamps + lb->slots;
+    lb->device_bytes += bytes;
+    if (lb->d_spare) {
+      const int rc = xsknf_gpu::lb_want_spare(lb);   // the spare table's stamps
+      if (rc) {
+        (void)hipFree(d);
+        lb->d_stamps = lb->d_clock = nullptr;
+        lb->device_bytes -= bytes;
+        free(st);
+        free(ls);
+        return rc;
+      }
+    }
+  }
+#endif
+  lb->stamps = st;
+  lb->live_s = ls;
+  lb->clock = 0;
+  return 0;
+}
+
+int xsknf_gpu_lb_clock(struct xsknf_gpu_lb *lb, int which, uint32_t now, void *stream) {
+  if (!lb || !lb->stamps || (which != XSKNF_GPU_LB_HOST_TABLE && which != XSKNF_GPU_LB_DEVICE_TABLE)) return -EINVAL;
+  if (which == XSKNF_GPU_LB_HOST_TABLE) {
+    lb->clock = now;
+    return 0;
+  }
+  if (!lb->d_svc) return -ENODEV;
+#ifndef XSKNF_LB_HOST_ONLY
+  // one 4-byte fill in stream order: nothing of the caller's is referenced later
+  const hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(lb->d_clock), static_cast<int>(now), 1,
+                                         static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return hip_rc(e, "load balancer clock");
+  return 0;
+#else
+  (void)stream;
+  return -ENODEV;
+#endif
+}
+
+int xsknf_gpu_lb_sessions_expire_host(struct xsknf_gpu_lb *lb, uint32_t max_idle, uint64_t *result) {
+  if (!lb || !lb->stamps) return -EINVAL;
+  report(result, 0, 0);
+  const int rc = want_scratch(lb);
+  if (rc) return rc;
+  // One pass in slot order gives the set semantics, as one launch does on the
+  // device (kernel_lb_expire.h): nothing a decision reads -- the stamps, a slot's
+  // key words a, b, c and its value -- changes here; only p does, to the
+  // tombstone.  So a session can miss its partner only where the partner has
+  // just been buried, which took both halves idle: this session's own verdict.
+  uint64_t removed = 0;
+  for (uint32_t s = 0; s < lb->slots; ++s) {
+    const Key k = lb->keys[s];
+    if (!live(k) || !idle(lb->clock, lb->stamps[s], max_idle)) continue;
+    const Val v = lb->vals[s];
+    const Key pk = partner_key(k, v);
+    const uint32_t ps = find(lb->keys, lb->slots, pk);
+    if (ps != kNone && is_partner(pk, lb->vals[ps], k, v) && !idle(lb->clock, lb->stamps[ps], max_idle)) continue;
+    bury(lb, s);
+    ++removed;
+  }
+  report(result, removed, settle(lb));
+  return 0;
+}
+
+int xsknf_gpu_lb_sessions_expire(struct xsknf_gpu_lb *lb, uint32_t max_idle, uint64_t *result_dev, void *stream) {
+  if (!lb || !lb->stamps || (reinterpret_cast<uintptr_t>(result_dev) & 7)) return -EINVAL;
+  if (!lb->d_svc) return -ENODEV;
+#ifndef XSKNF_LB_HOST_ONLY
+  return xsknf_gpu::lb_expire_enqueue(lb, max_idle, result_dev, stream);
+#else
+  (void)max_idle, (void)stream;
+  return -ENODEV;
+#endif
+}
+
+int xsknf_gpu_lb_sessions_ages(const struct xsknf_gpu_lb *lb, int which, struct xsknf_gpu_lb_session_key *keys,
+                               uint32_t *ages, uint32_t cap, uint32_t *n_out, uint32_t *clock_out) {
+  if (!lb || !lb->stamps || !n_out || (cap && (!keys || !ages))) return -EINVAL;
+  if (which == XSKNF_GPU_LB_HOST_TABLE) {
+    if (clock_out) *clock_out = lb->clock;
+    return dump_table(lb->keys, lb->vals, lb->slots, keys, nullptr, cap, n_out, lb->stamps, lb->clock, ages);
+  }
+  if (which != XSKNF_GPU_LB_DEVICE_TABLE) return -EINVAL;
+  if (!lb->d_svc) return -ENODEV;
+#ifndef XSKNF_LB_HOST_ONLY
+  const size_t kb = sizeof(Key) * static_cast<size_t>(lb->slots);
+  const size_t sb = sizeof(uint32_t) * (static_cast<size_t>(lb->slots) + 1);   // the stamps and the clock behind them
+  char *tmp = static_cast<char *>(malloc(kb + sb));
+  if (!tmp) return -ENOMEM;
+  uint32_t *st = reinterpret_cast<uint32_t *>(tmp + kb);
+  hipError_t e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(tmp, lb->d_keys, kb, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(st, lb->d_stamps, sb, hipMemcpyDeviceToHost);
+  int rc;
+  if (e == hipSuccess) {
+    if (clock_out) *clock_out = st[lb->slots];
+    rc = dump_table(reinterpret_cast<Key *>(tmp), nullptr, lb->slots, keys, nullptr, cap, n_out, st, st[lb->slots], ages);
+  } else {
+    rc = hip_rc(e, "load balancer sessions_ages");
+  }
+  free(tmp);
+  return rc;
+#else
   return -ENODEV;
 #endif
 }

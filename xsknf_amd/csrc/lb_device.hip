@@ -15,6 +15,9 @@
 //   apply    sessions resolved, frames rewritten, verdicts
 //   commit   the new sessions stored
 //   ordered  one lane: the count, or the whole loop for a batch that stood down
+// and, for an object with ageing alone (xsknf_gpu_lb_aging_enable), a fifth
+// between commit and ordered (kernel_lb_stamp.h):
+//   stamp    rule 11: the hit and the new sessions' last-seen stamps
 // A translation unit of its own: none of the other kernels is rebuilt for it.
 //
 // Workspace: [16 header words][staging: S words, S the power of two >= 4 n, at
@@ -25,6 +28,7 @@
 
 #include "checksummer_internal.h"
 #include "kernel_lb.h"
+#include "kernel_lb_stamp.h"
 
 namespace {
 
@@ -54,7 +58,8 @@ int run_batch(uint8_t *umem, uint64_t umem_size, const struct xsknf_gpu_desc *de
   a.umem_size = umem_size;
   a.descs = reinterpret_cast<const uint4 *>(descs);
   a.verdicts = verdicts;
-  a.t = lb::Tables{lb->d_svc, lb->d_bk, lb->d_keys, lb->d_vals, lb->d_count, lb->svc_slots, lb->slots, lb->max_sessions};
+  a.t = lb::Tables{lb->d_svc,     lb->d_bk,  lb->d_keys,       lb->d_vals,   lb->d_count,
+                   lb->svc_slots, lb->slots, lb->max_sessions, lb->d_stamps, lb->d_clock};   // (stamps: NULL without ageing)
   a.stage_slots = stage_slots(n);
   char *w = static_cast<char *>(workspace);
   a.hdr = reinterpret_cast<uint32_t *>(w);
@@ -75,6 +80,7 @@ int run_batch(uint8_t *umem, uint64_t umem_size, const struct xsknf_gpu_desc *de
     else hipLaunchKernelGGL(lbk::lb_propose<false>, grid, dim3(lbk::kThreads), 0, s, a);
     hipLaunchKernelGGL(lbk::lb_apply, grid, dim3(lbk::kThreads), 0, s, a);
     hipLaunchKernelGGL(lbk::lb_commit, grid, dim3(lbk::kThreads), 0, s, a);
+    if (a.t.stamps) hipLaunchKernelGGL(lbk::lb_stamp, grid, dim3(lbk::kThreads), 0, s, a);
     hipLaunchKernelGGL(lbk::lb_ordered, dim3(1), dim3(64), 0, s, a);
     e = hipGetLastError();
   }

@@ -22,7 +22,8 @@ int xsknf_gpu_lb_host(uint8_t *umem, uint64_t umem_size, const struct xsknf_gpu_
   if (!lb) return -EINVAL;
   if (n && (!umem || !descs || !verdicts)) return -EINVAL;
   uint64_t st[lb::kStats] = {0};
-  const lb::Tables t = {lb->svc, lb->bk, lb->keys, lb->vals, &lb->count, lb->svc_slots, lb->slots, lb->max_sessions};
+  const lb::Tables t = {lb->svc,       lb->bk,    lb->keys,         lb->vals,   &lb->count,
+                        lb->svc_slots, lb->slots, lb->max_sessions, lb->stamps, &lb->clock};   // (stamps: rule 11, or NULL)
   const lb::Gate none = {nullptr, nullptr, 0};
   const int32_t pass = lb::pass_verdict(ingress_ifindex, num_interfaces);
   st[lb::kFrames] = n;

@@ -1,8 +1,8 @@
 // lb_remove_device.hip -- removing sessions from the load balancer's device table
 // (include/xsknf_gpu.h xsknf_gpu_lb_sessions_remove, _drain_backend,
-// _drain_backends, _sessions_clear; lb.cpp validates and calls the functions
-// below, which lb_table.h declares; the kernels are kernel_lb_remove.h's and
-// kernel_lb_drain_list.h's).
+// _drain_backends, _sessions_expire, _sessions_clear; lb.cpp validates and calls
+// the functions below, which lb_table.h declares; the kernels are
+// kernel_lb_remove.h's, kernel_lb_drain_list.h's and kernel_lb_expire.h's).
 //
 // Everything is enqueued on the caller's stream and nothing is read back:
 //   remove  [result zeroed] one async copy of the key list, 16 B per key, from a
@@ -12,6 +12,7 @@
 //   drain   [result zeroed] lb_drain over the slots and the same four launches
 //   drain a list  [result zeroed] one async copy of the listed backends as a set,
 //           8 B per slot, lb_drain_list over the slots and the same four launches
+//   expire  [result zeroed] lb_expire over the slots and the same four launches
 //   clear   one memset over the keys, the values and the two counters
 //
 // The caller's key list is host memory that the call must not reference after it
@@ -25,7 +26,9 @@
 // The spare table a compaction rebuilds into -- as large as the session table's
 // keys and values -- is allocated by the first removal and is part of
 // device_bytes from then on.  It needs no contents: lb_compact_zero clears it
-// when it is used.  A translation unit of its own: none of the other kernels is
+// when it is used.  With ageing the spare table has stamps of its own, 4 B per
+// slot, allocated with it or, where it came first, by _aging_enable.  A
+// translation unit of its own: none of the other kernels is
 // rebuilt for it.
 #include <errno.h>
 #include <string.h>
@@ -35,6 +38,7 @@
 
 #include "checksummer_internal.h"
 #include "kernel_lb_drain_list.h"
+#include "kernel_lb_expire.h"
 #include "kernel_lb_remove.h"
 #include "lb_stage.h"
 
@@ -122,18 +126,29 @@ int lb_stage_acquire(xsknf_gpu_lb *lb, size_t bytes, LbStage **out) {
   return 0;
 }
 
-namespace {
-
-int want_spare(xsknf_gpu_lb *lb) {
-  if (lb->d_spare) return 0;
-  const size_t bytes = (sizeof(lb::Key) + sizeof(lb::Val)) * static_cast<size_t>(lb->slots);
-  void *d = nullptr;
-  const hipError_t e = hipMalloc(&d, bytes);
-  if (e != hipSuccess) return hip_rc(e, "load balancer spare table");
-  lb->d_spare = static_cast<lb::Key *>(d);
-  lb->device_bytes += bytes;
+int lb_want_spare(xsknf_gpu_lb *lb) {
+  if (!lb->d_spare) {
+    const size_t bytes = (sizeof(lb::Key) + sizeof(lb::Val)) * static_cast<size_t>(lb->slots);
+    void *d = nullptr;
+    const hipError_t e = hipMalloc(&d, bytes);
+    if (e != hipSuccess) return hip_rc(e, "load balancer spare table");
+    lb->d_spare = static_cast<lb::Key *>(d);
+    lb->device_bytes += bytes;
+  }
+  if (lb->d_stamps && !lb->d_spare_stamps) {
+    const size_t bytes = sizeof(uint32_t) * static_cast<size_t>(lb->slots);
+    void *d = nullptr;
+    const hipError_t e = hipMalloc(&d, bytes);
+    if (e != hipSuccess) return hip_rc(e, "load balancer spare stamps");
+    lb->d_spare_stamps = static_cast<uint32_t *>(d);
+    lb->device_bytes += bytes;
+  }
   return 0;
 }
+
+namespace {
+
+int want_spare(xsknf_gpu_lb *lb) { return lb_want_spare(lb); }
 
 lbr::Args table_args(const xsknf_gpu_lb *lb, uint64_t *result_dev) {
   lbr::Args a;
@@ -145,6 +160,9 @@ lbr::Args table_args(const xsknf_gpu_lb *lb, uint64_t *result_dev) {
   a.count = lb->d_count;
   a.result = reinterpret_cast<unsigned long long *>(result_dev);
   a.slots = lb->slots;
+  a.stamps = lb->d_stamps;
+  a.spare_stamps = lb->d_spare_stamps;
+  a.clock = lb->d_clock;
   return a;
 }
 
@@ -237,6 +255,21 @@ int lb_drain_list_enqueue(xsknf_gpu_lb *lb, const void *set, uint32_t set_slots,
   return 0;
 }
 
+int lb_expire_enqueue(xsknf_gpu_lb *lb, uint32_t max_idle, uint64_t *result_dev, void *stream) {
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  const int rc = want_spare(lb);
+  if (rc) return rc;
+  hipError_t e = result_dev ? hipMemsetAsync(result_dev, 0, sizeof(uint64_t) * XSKNF_GPU_LB_REMOVE_RESULT, s) : hipSuccess;
+  if (e != hipSuccess) return hip_rc(e, "load balancer expire");
+  lbr::Args a = table_args(lb, result_dev);
+  a.max_idle = max_idle;
+  hipLaunchKernelGGL(lbr::lb_expire, grid_for(a.slots), dim3(lbr::kThreads), 0, s, a);
+  enqueue_compaction(a, s);
+  e = hipGetLastError();
+  if (e != hipSuccess) return hip_rc(e, "load balancer expire");
+  return 0;
+}
+
 int lb_clear_enqueue(xsknf_gpu_lb *lb, void *stream) {
   // keys, values and the 16 bytes behind them (lb.cpp's one allocation): the count and the tombstones
   const size_t bytes = (sizeof(lb::Key) + sizeof(lb::Val)) * static_cast<size_t>(lb->slots) + 16;
@@ -259,6 +292,11 @@ int lb_remove_release(xsknf_gpu_lb *lb) {
     const hipError_t e = hipFree(lb->d_spare);
     if (e != hipSuccess) rc = hip_rc(e, "load balancer release");
     lb->d_spare = nullptr;
+  }
+  if (lb->d_spare_stamps) {
+    const hipError_t e = hipFree(lb->d_spare_stamps);
+    if (e != hipSuccess) rc = hip_rc(e, "load balancer release");
+    lb->d_spare_stamps = nullptr;
   }
   return rc;
 }

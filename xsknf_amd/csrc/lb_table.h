@@ -70,7 +70,15 @@ struct Tables {
   Val *vals;
   uint32_t *count;          // sessions stored
   uint32_t svc_slots, slots, max_sessions;
+  // ageing (rule 11; xsknf_gpu_lb_aging_enable): one last-seen stamp per slot, a
+  // side array, and the table's clock word.  stamps == nullptr: no ageing.
+  uint32_t *stamps;
+  const uint32_t *clock;
 };
+// Rule 11: slot s has been used, or stored into, at the table's clock.
+XSKNF_HD inline void stamp(const Tables &t, uint32_t s) {
+  if (t.stamps) t.stamps[s] = *t.clock;
+}
 
 // The slot that holds k, or kNone.
 XSKNF_HD inline uint32_t find(const Key *keys, uint32_t slots, const Key &k) {
@@ -87,7 +95,8 @@ XSKNF_HD inline uint32_t find(const Key *keys, uint32_t slots, const Key &k) {
 
 // khashmap_update_elem on one thread: the value of a stored key is replaced; a
 // new key is stored unless the table already holds max_sessions (-1).  Returns
-// 1 for a new key, 0 for a replaced value.
+// 1 for a new key, 0 for a replaced value.  With ageing either one stamps the
+// slot (rule 11); a refused key stamps nothing.
 XSKNF_HD inline int put(const Tables &t, const Key &k, const Val &v) {
   const uint32_t mask = t.slots - 1;
   uint32_t s = key_hash(k) & mask;
@@ -98,10 +107,12 @@ XSKNF_HD inline int put(const Tables &t, const Key &k, const Val &v) {
       t.keys[s] = k;
       t.vals[s] = v;
       ++*t.count;
+      stamp(t, s);
       return 1;
     }
     if (same(h, k)) {
       t.vals[s] = v;
+      stamp(t, s);
       return 0;
     }
     s = (s + 1) & mask;
@@ -145,6 +156,11 @@ XSKNF_HD inline bool drains(const Key &k, const Val &v, uint32_t addr, uint32_t 
 struct IdSlot {
   uint32_t addr, pw;
 };
+// xsknf_gpu_lb_sessions_expire's idle(k): unsigned, so a clock that has wrapped
+// past a stamp still gives the ticks between them.
+XSKNF_HD inline bool idle(uint32_t clock, uint32_t stamp_of, uint32_t max_idle) {
+  return static_cast<uint32_t>(clock - stamp_of) > max_idle;
+}
 XSKNF_HD inline IdSlot drain_candidate(const Key &k, const Val &v) {
   return dir_of(v) == kToBackend ? IdSlot{v.addr, (v.pi & 0xffff) | k.p << 16} : IdSlot{k.a, (k.c & 0xffff) | k.p << 16};
 }
@@ -345,6 +361,7 @@ XSKNF_HD inline int32_t frame(const Tables &t, const Gate &gate, uint8_t *f, uin
   const uint32_t s = find(t.keys, t.slots, sid);
   if (s != kNone) {
     rep = t.vals[s];
+    stamp(t, s);   // rule 11
   } else {
     const Service *svc = find_service(t.svc, t.svc_slots, sid.b, (sid.c >> 16) | proto << 16);
     if (!svc) {
@@ -391,6 +408,11 @@ struct xsknf_gpu_lb {
   uint32_t tombstones;                 // host table: slots that hold kTombstoneP
   xsknf_gpu::lb::Key *live_k;          // host: room for max_sessions sessions while the table is rebuilt
   xsknf_gpu::lb::Val *live_v;          //   (NULL until the first host removal)
+  // ageing (all NULL / 0 until xsknf_gpu_lb_aging_enable): the host table's
+  // stamps, one per slot, its clock, and the stamps' room in a rebuild
+  uint32_t *stamps;
+  uint32_t clock;
+  uint32_t *live_s;
   // device (all NULL in a host-only object): d_base is creation's one
   // allocation -- services, backends, keys, values, counters.  d_svc / d_bk
   // point into it until the first update, then into d_region
@@ -409,6 +431,12 @@ struct xsknf_gpu_lb {
   // calls in flight (removals, list drains, updates)
   xsknf_gpu::lb::Key *d_spare;
   struct xsknf_gpu_lb_staging *staging;
+  // ageing on the device (NULL until _aging_enable): one allocation, `slots`
+  // stamps and behind them the clock word; and the spare table's stamps (with
+  // d_spare, once both ageing and a device removal have happened)
+  uint32_t *d_stamps;
+  uint32_t *d_clock;
+  uint32_t *d_spare_stamps;
 };
 
 #ifndef XSKNF_LB_HOST_ONLY
@@ -423,6 +451,11 @@ int lb_drain_enqueue(xsknf_gpu_lb *lb, uint32_t addr, uint32_t port, uint32_t pr
 // empty), host memory that is copied before the call returns.
 int lb_drain_list_enqueue(xsknf_gpu_lb *lb, const void *set, uint32_t set_slots, uint64_t *result_dev, void *stream);
 int lb_clear_enqueue(xsknf_gpu_lb *lb, void *stream);
+// Ageing (the object has stamps): the expiry pass over the device table and the
+// four compaction launches; the spare table with the stamps' part, where it is
+// missing (_aging_enable calls it when a spare table already exists).
+int lb_expire_enqueue(xsknf_gpu_lb *lb, uint32_t max_idle, uint64_t *result_dev, void *stream);
+int lb_want_spare(xsknf_gpu_lb *lb);
 int lb_remove_release(xsknf_gpu_lb *lb);   // _destroy
 
 // lb_backends_device.hip: an update's way to the device copy.  _prepare makes

@@ -19,7 +19,10 @@ are what route.route_batch consumes.  Sessions end through
 are enqueued between batches and wait for nothing.  The services and backends
 change under traffic through `LoadBalancer.backends_update`
 (xsknf_amd/csrc/lb_backends_device.hip for the device copy), and
-`drain_backends` ends the flows of a list of backends in one pass.
+`drain_backends` ends the flows of a list of backends in one pass.  With
+`LoadBalancer.aging_enable` every session carries a last-seen stamp that the
+batches write; `clock` sets a table's clock and `expire` ends the flows that
+have been idle too long (xsknf_amd/csrc/kernel_lb_stamp.h, kernel_lb_expire.h).
 """
 from __future__ import annotations
 
@@ -254,6 +257,59 @@ class LoadBalancer:
         _lib.check(_lib.load().xsknf_gpu_lb_drain_backends(self.handle, ip, i.size, res.data_ptr(),
                                                            ctypes.c_void_p(s or None)), "xsknf_gpu_lb_drain_backends")
         return res
+
+    def aging_enable(self) -> None:
+        """xsknf_gpu_lb_aging_enable: a last-seen stamp per session and a clock
+        per table, from now on (rule 11).  Only with no batch in flight; a
+        second call changes nothing."""
+        _lib.check(_lib.load().xsknf_gpu_lb_aging_enable(self.handle), "xsknf_gpu_lb_aging_enable")
+
+    def clock(self, now: int, *, which: int = DEVICE_TABLE, stream=None) -> None:
+        """xsknf_gpu_lb_clock: one table's clock becomes `now` (uint32, the
+        caller's unit); the device table's on `stream` (default: the current
+        stream), in order with the batches there, waiting for nothing."""
+        s = 0
+        if which == DEVICE_TABLE and self._has_device_half():
+            import torch
+
+            s = int(getattr(stream, "cuda_stream", stream)) if stream is not None else torch.cuda.current_stream().cuda_stream
+        _lib.check(_lib.load().xsknf_gpu_lb_clock(self.handle, which, now & 0xffffffff, ctypes.c_void_p(s or None)),
+                   "xsknf_gpu_lb_clock")
+
+    def expire(self, max_idle: int, *, which: int = DEVICE_TABLE, stream=None):
+        """xsknf_gpu_lb_sessions_expire / _expire_host: every flow whose
+        sessions have all been idle for more than `max_idle` ticks of the
+        table's clock leaves one session table.  Returns the result words as
+        `sessions_remove` does."""
+        if which == HOST_TABLE:
+            res = np.zeros(_lib.LB_REMOVE_RESULT, dtype=np.uint64)
+            _lib.check(_lib.load().xsknf_gpu_lb_sessions_expire_host(self.handle, max_idle, res.ctypes.data),
+                       "xsknf_gpu_lb_sessions_expire_host")
+            return res
+        if which != DEVICE_TABLE:
+            raise ValueError("which must be HOST_TABLE or DEVICE_TABLE")
+        if not self._has_device_half():   # (no tensor to make: the call itself says -EINVAL or -ENODEV)
+            _lib.check(_lib.load().xsknf_gpu_lb_sessions_expire(self.handle, max_idle, None, None),
+                       "xsknf_gpu_lb_sessions_expire")
+        res, s = self._device_result(stream)
+        _lib.check(_lib.load().xsknf_gpu_lb_sessions_expire(self.handle, max_idle, res.data_ptr(),
+                                                            ctypes.c_void_p(s or None)), "xsknf_gpu_lb_sessions_expire")
+        return res
+
+    def sessions_ages(self, which: int = HOST_TABLE):
+        """xsknf_gpu_lb_sessions_ages: (keys, ages uint32, clock) of the host or
+        the device table, ascending by key as `sessions_dump`; an age is the
+        table's clock minus the session's stamp.  Waits for the device."""
+        lib = _lib.load()
+        n, clock = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        rc = lib.xsknf_gpu_lb_sessions_ages(self.handle, which, None, None, 0, ctypes.byref(n), ctypes.byref(clock))
+        if rc not in (0, -errno.ENOSPC):
+            _lib.check(rc, "xsknf_gpu_lb_sessions_ages")
+        k, a = np.zeros(int(n.value), dtype=KEY_DTYPE), np.zeros(int(n.value), dtype=np.uint32)
+        if k.size:
+            _lib.check(lib.xsknf_gpu_lb_sessions_ages(self.handle, which, k.ctypes.data, a.ctypes.data, k.size,
+                                                      ctypes.byref(n), ctypes.byref(clock)), "xsknf_gpu_lb_sessions_ages")
+        return k, a, int(clock.value)
 
     def sessions_clear(self, which: int, *, stream=None) -> None:
         """xsknf_gpu_lb_sessions_clear: every session of one table; the device
