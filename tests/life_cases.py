@@ -178,9 +178,9 @@ def stand_down(M, umem, descs, acl):
 class World:
     """Everything the script's objects hold, and apply(op): the model's run of one op."""
 
-    def __init__(self, shape, backends, rules):
+    def __init__(self, shape, backends, rules, sessions=Sessions):
         self.shape = shape
-        self.M = Sessions(backends, shape.max_sessions, shape.slots)
+        self.M = sessions(backends, shape.max_sessions, shape.slots)
         self.acl = FC.acl_dict(rules)
         self.slots = AclSlots(shape.acl_slots, rules)
         self._dump = self.M.dump()
@@ -218,7 +218,7 @@ class World:
         elif op.kind == "sessions_put":
             M.sessions_put(op.keys, op.values)
         else:
-            raise ValueError(op.kind)
+            self.other(op, w)
         if op.kind in REMOVALS:
             w.removed = set(before) - set(M.sessions)
         if M.sessions != before:
@@ -228,6 +228,10 @@ class World:
         w.acl_rules, w.acl_tombstones = self._rules, self.slots.tombstones
         op.want = w
         return w
+
+    def other(self, op, w):
+        """The op kinds of a later generation of scripts (tests/churn_cases.py)."""
+        raise ValueError(op.kind)
 
 
 # ---- the universe and the generator --------------------------------------------------
