@@ -669,7 +669,7 @@ struct xsknf_gpu_acl_info {
 	uint32_t slots;          /* key slots (a power of two > rules) */
 	uint32_t max_probe;      /* slots looked at for the worst-placed rule (0 for an empty ACL), kept across updates */
 	uint32_t tombstones;     /* slots that mark a deleted key (xsknf_gpu_acl_update); 0 after _create */
-	uint64_t device_bytes;   /* 20 * slots (0: built where no device was visible) */
+	uint64_t device_bytes;   /* 20 * slots, and the hit counters' share once enabled (0: built where no device was visible) */
 };
 
 /* Read the reference's ACL text (init_acl, firewall_user.c:53-116): the rule
@@ -771,6 +771,75 @@ XSKNF_GPU_API int xsknf_gpu_acl_update(struct xsknf_gpu_acl *acl, const struct x
 #define XSKNF_GPU_ACL_DEVICE_TABLE 1
 XSKNF_GPU_API int xsknf_gpu_acl_dump(const struct xsknf_gpu_acl *acl, int which, struct xsknf_gpu_acl_rule *rules_out,
 		uint32_t cap, uint32_t *n_out);
+
+/* Per-rule hit counters, as `iptables -v` and nft counters give them: opt-in
+ * per ACL object.  An ACL that never calls _counters_enable behaves, allocates,
+ * sends update records and launches exactly as without these calls.
+ *
+ * _counters_enable (with no batch and no update in flight; idempotent) gives
+ * each table, host and device, one {packets, bytes} pair of uint64_t per slot as
+ * a side array -- the 16-byte key slots and the action array keep their layout
+ * -- and XSKNF_GPU_ACL_TOTALS uint64_t totals, all 0.  The device's share is
+ * 16 bytes per slot plus 32 for the totals, part of device_bytes from this
+ * call on; the first update that rebuilds the table (below) adds a second
+ * counter array and a slot map, 20 bytes per slot more, from then on.
+ *
+ * Two independent sets, like the load balancer's two session tables: the host
+ * set counts the frames of xsknf_gpu_firewall_host and xsknf_gpu_lbfw_host, the
+ * device set those of xsknf_gpu_firewall_batch and xsknf_gpu_lbfw_batch, and
+ * neither is ever copied into the other.  The host calls take the ACL as const
+ * and still add to its host set, with plain adds: on an ACL with counters they
+ * must be made one at a time (without counters they only read, as before).
+ *
+ * A frame that reaches rule 7 (in lbfw: rule 6a, the gate) and finds its key
+ * adds 1 to that rule's packets and its descriptor's len to that rule's bytes,
+ * whatever the action, 0 included.  The totals, over every frame handed to
+ * such a call:
+ *   [0] frames
+ *   [1] frames that hit a rule
+ *   [2] frames that reached the lookup and found no rule (in lbfw: the frames
+ *       that go on to the load balancer)
+ *   [3] frames decided before the lookup (rules 0-5, outside the UMEM)
+ * [0] = [1] + [2] + [3], and [1] equals the sum of packets over the rules that
+ * were live for the whole interval.  All adds are integer adds, exact whatever
+ * their order; on the device they are device-scope atomics, so two batches on
+ * two streams that read the same ACL both count in full.  A batch enqueued
+ * before an update counts against the old rules, one enqueued after it against
+ * the new ones.  An lbfw batch counts each frame once, whichever of its paths
+ * it takes (the gate decides a frame in one place only).
+ *
+ * Updates, per table, in op order within a call: a PUT of a key the map holds
+ * keeps that key's counters (replacing an action is not a new rule); a DELETE
+ * of a present key ends them; a PUT of an absent key starts at 0/0 -- so DELETE
+ * k followed by PUT k in one call resets k, even where k lands in the same
+ * slot.  A rebuild carries every surviving key's counters to its new slot,
+ * also past the puts and deletes of the same call.  The host table does all
+ * this at once, the device table in stream order: the host waits for nothing
+ * and reads nothing back, and once the stream has passed the update the
+ * device's per-key counters are what applying the ops between the two
+ * neighbouring batches gives.
+ *
+ * -EINVAL for NULL; -ENOMEM; -EIO on a HIP error.  A host-only object enables
+ * and counts on the host alone. */
+#define XSKNF_GPU_ACL_TOTALS 4
+struct xsknf_gpu_acl_counter {
+	uint64_t packets, bytes;
+};
+XSKNF_GPU_API int xsknf_gpu_acl_counters_enable(struct xsknf_gpu_acl *acl);
+/* xsknf_gpu_acl_dump with counters_out[i] the counters of rules_out[i]: the
+ * same order, cap, *n_out and -ENOSPC, -ENODEV for the device set of a
+ * host-only object; the device form waits for the device.  totals_out (may be
+ * NULL) receives the set's XSKNF_GPU_ACL_TOTALS totals.  -EINVAL, before any
+ * work: a NULL acl, an object without counters, another `which`, a NULL n_out,
+ * a NULL rules_out or counters_out with cap > 0. */
+XSKNF_GPU_API int xsknf_gpu_acl_counters_dump(const struct xsknf_gpu_acl *acl, int which,
+		struct xsknf_gpu_acl_rule *rules_out, struct xsknf_gpu_acl_counter *counters_out, uint32_t cap,
+		uint32_t *n_out, uint64_t *totals_out);
+/* Zero one set, counters and totals: the host set at once, the device set in
+ * stream order on `stream` (ignored for the host set).  -EINVAL for a NULL acl,
+ * an object without counters or another `which`; -ENODEV for the device set of
+ * a host-only object; -EIO. */
+XSKNF_GPU_API int xsknf_gpu_acl_counters_clear(struct xsknf_gpu_acl *acl, int which, void *stream);
 
 /* verdicts[i] = the firewall's verdict for descs[i], i < n, on the current
  * device (the one the ACL was created on), asynchronously on `stream` (a

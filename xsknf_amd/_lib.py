@@ -63,6 +63,9 @@ EXPORTED_SYMBOLS = (
     "xsknf_gpu_acl_destroy",
     "xsknf_gpu_acl_update",
     "xsknf_gpu_acl_dump",
+    "xsknf_gpu_acl_counters_enable",
+    "xsknf_gpu_acl_counters_dump",
+    "xsknf_gpu_acl_counters_clear",
     "xsknf_gpu_firewall_batch",
     "xsknf_gpu_firewall_host",
     "xsknf_gpu_lb_create",
@@ -112,6 +115,7 @@ ACL_PUT = 0                 # XSKNF_GPU_ACL_PUT, the op of struct xsknf_gpu_acl_
 ACL_DELETE = 1
 ACL_HOST_TABLE = 0          # xsknf_gpu_acl_dump's `which`
 ACL_DEVICE_TABLE = 1
+ACL_TOTALS = 4              # XSKNF_GPU_ACL_TOTALS: frames, hits, misses, decided before the lookup
 
 ROUTE_MAX_INTERFACES = 32   # XSKNF_GPU_ROUTE_MAX_INTERFACES
 FORWARD_STATS = 3           # XSKNF_GPU_FORWARD_STATS
@@ -359,6 +363,12 @@ def load() -> ctypes.CDLL:
     lib.xsknf_gpu_acl_update.argtypes = [vp, vp, ctypes.c_uint32, vp]
     lib.xsknf_gpu_acl_dump.restype = ctypes.c_int
     lib.xsknf_gpu_acl_dump.argtypes = [vp, ctypes.c_int, vp, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
+    lib.xsknf_gpu_acl_counters_enable.restype = ctypes.c_int
+    lib.xsknf_gpu_acl_counters_enable.argtypes = [vp]
+    lib.xsknf_gpu_acl_counters_dump.restype = ctypes.c_int
+    lib.xsknf_gpu_acl_counters_dump.argtypes = [vp, ctypes.c_int, vp, vp, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), vp]
+    lib.xsknf_gpu_acl_counters_clear.restype = ctypes.c_int
+    lib.xsknf_gpu_acl_counters_clear.argtypes = [vp, ctypes.c_int, vp]
     lib.xsknf_gpu_firewall_batch.restype = ctypes.c_int
     lib.xsknf_gpu_firewall_batch.argtypes = [vp, u64, vp, ctypes.c_uint32, vp, vp, vp]
     lib.xsknf_gpu_firewall_host.restype = ctypes.c_int

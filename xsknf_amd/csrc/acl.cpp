@@ -76,15 +76,19 @@ void free_acl(xsknf_gpu_acl *acl) {
   free(acl->keys);
   free(acl->actions);
   free(acl->probe_hist);
+  free(acl->ctr);   // (the totals lie behind the counters)
   delete acl;
 }
 
 // ---- updates ------------------------------------------------------------------
 
+using xsknf_gpu::AclCounter;
 using xsknf_gpu::kAclNone;
 using xsknf_gpu::kAclTombstoneP;
 
 constexpr AclKey kTombstone = {0, 0, 0, kAclTombstoneP};
+static_assert(xsknf_gpu::kAclTotals == XSKNF_GPU_ACL_TOTALS, "the totals of include/xsknf_gpu.h");
+static_assert(XSKNF_GPU_ACL_MAX_SLOTS <= xsknf_gpu::kAclRecSlotMask, "a slot number leaves AclUpdateRec's flag bit free");
 
 inline AclKey key_of(const struct xsknf_gpu_acl_rule &r) {
   return AclKey{r.saddr, r.daddr, static_cast<uint32_t>(r.sport) | static_cast<uint32_t>(r.dport) << 16, r.proto};
@@ -117,15 +121,27 @@ Place place_of(const xsknf_gpu_acl *acl, const AclKey &k) {
 
 // The same slot count, the live rules reinserted in ascending slot order of the
 // old table, no tombstone left.  live_k / live_a: room for acl->rules entries.
-void rebuild_in_place(xsknf_gpu_acl *acl, AclKey *live_k, int32_t *live_a) {
+// With counters, live_c and live_s as well: every key's counters go with it,
+// and from[s] (`slots` entries) becomes the old slot of new slot s's key, or
+// kAclNone -- the map the device's counters are carried by.
+void rebuild_in_place(xsknf_gpu_acl *acl, AclKey *live_k, int32_t *live_a, AclCounter *live_c, uint32_t *live_s,
+                      uint32_t *from) {
   uint32_t n = 0;
   for (uint32_t s = 0; s < acl->slots; ++s)
     if (live(acl->keys[s])) {
       live_k[n] = acl->keys[s];
+      if (acl->ctr) {
+        live_c[n] = acl->ctr[s];
+        live_s[n] = s;
+      }
       live_a[n++] = acl->actions[s];
     }
   memset(acl->keys, 0, sizeof(AclKey) * acl->slots);
   memset(acl->actions, 0, sizeof(int32_t) * acl->slots);
+  if (acl->ctr) {
+    memset(acl->ctr, 0, sizeof(AclCounter) * acl->slots);
+    for (uint32_t s = 0; s < acl->slots; ++s) from[s] = kAclNone;
+  }
   memset(acl->probe_hist, 0, sizeof(uint32_t) * (static_cast<size_t>(acl->max_probe) + 1));
   acl->max_probe = 0;
   acl->tombstones = 0;
@@ -139,14 +155,19 @@ void rebuild_in_place(xsknf_gpu_acl *acl, AclKey *live_k, int32_t *live_a) {
     }
     acl->keys[s] = k;
     acl->actions[s] = live_a[i];
+    if (acl->ctr) {
+      acl->ctr[s] = live_c[i];
+      from[s] = live_s[i];
+    }
     ++acl->probe_hist[probes];
     if (probes > acl->max_probe) acl->max_probe = probes;
   }
 }
 
 // the live rules of a table, ascending by key
+// (and, with ctr, each rule's counters into ctr_out)
 int dump_table(const AclKey *keys, const int32_t *actions, uint32_t slots, struct xsknf_gpu_acl_rule *out, uint32_t cap,
-               uint32_t *n_out) {
+               uint32_t *n_out, const AclCounter *ctr = nullptr, struct xsknf_gpu_acl_counter *ctr_out = nullptr) {
   std::vector<uint32_t> used;
   try {
     for (uint32_t s = 0; s < slots; ++s)
@@ -173,6 +194,7 @@ int dump_table(const AclKey *keys, const int32_t *actions, uint32_t slots, struc
     r.proto = static_cast<uint8_t>(k.p);
     r.action = actions[used[i]];
     out[i] = r;
+    if (ctr) ctr_out[i] = {ctr[used[i]].packets, ctr[used[i]].bytes};
   }
   return used.size() > cap ? -ENOSPC : 0;
 }
@@ -309,7 +331,7 @@ int xsknf_gpu_acl_info(const struct xsknf_gpu_acl *acl, struct xsknf_gpu_acl_inf
   info->slots = acl->slots;
   info->max_probe = acl->max_probe;
   info->tombstones = acl->tombstones;
-  info->device_bytes = acl->d_keys ? (sizeof(AclKey) + sizeof(int32_t)) * static_cast<uint64_t>(acl->slots) : 0;
+  info->device_bytes = acl->d_keys ? (sizeof(AclKey) + sizeof(int32_t)) * static_cast<uint64_t>(acl->slots) + acl->d_ctr_bytes : 0;
   return 0;
 }
 
@@ -319,6 +341,7 @@ int xsknf_gpu_acl_destroy(struct xsknf_gpu_acl *acl) {
 #ifndef XSKNF_ACL_HOST_ONLY
   if (acl->d_keys) {
     rc = xsknf_gpu::acl_staging_release(acl);
+    if (xsknf_gpu::acl_counters_device_release(acl)) rc = -EIO;
     const hipError_t e = hipFree(acl->d_keys);
     if (e != hipSuccess) {
       xsknf_gpu::set_error(e, "ACL release");
@@ -342,12 +365,25 @@ int xsknf_gpu_acl_update(struct xsknf_gpu_acl *acl, const struct xsknf_gpu_acl_o
   // indices) is skipped.  What is left splits into the slots to delete and the
   // puts; both are applied in ascending op order, the deletes first, so the
   // table never holds more keys than before or after the call.
+  // With counters a PUT whose key is in the map keeps the key's counters unless
+  // an earlier op of the call deleted the key: again[i] marks such a final PUT.
   std::vector<uint32_t> seen, dels, puts, dirty;
+  std::vector<uint8_t> again;
   uint32_t n_new = 0;
   AclKey *live_k = nullptr;
   int32_t *live_a = nullptr;
+  AclCounter *live_c = nullptr;
+  uint32_t *live_s = nullptr, *from = nullptr;
   bool rebuild = false;
+  const auto drop = [&] {
+    free(live_k);
+    free(live_a);
+    free(live_c);
+    free(live_s);
+    free(from);
+  };
   try {
+    if (acl->ctr) again.assign(n, 0);
     size_t cap = 16;
     while (cap < 2 * static_cast<size_t>(n)) cap *= 2;
     seen.assign(cap, kAclNone);
@@ -357,7 +393,10 @@ int xsknf_gpu_acl_update(struct xsknf_gpu_acl *acl, const struct xsknf_gpu_acl_o
       const AclKey k = key_of(r);
       size_t s = xsknf_gpu::acl_hash(k.a, k.b, k.c, k.p) & (cap - 1);
       while (seen[s] != kAclNone && !same(key_of(ops[seen[s]].rule), k)) s = (s + 1) & (cap - 1);
-      if (seen[s] != kAclNone) continue;
+      if (seen[s] != kAclNone) {
+        if (acl->ctr && ops[i].op == XSKNF_GPU_ACL_DELETE) again[seen[s]] = 1;
+        continue;
+      }
       seen[s] = i;
       const uint32_t at = xsknf_gpu::acl_find(acl->keys, slots, k.a, k.b, k.c, k.p);
       if (ops[i].op == XSKNF_GPU_ACL_DELETE) {
@@ -381,24 +420,30 @@ int xsknf_gpu_acl_update(struct xsknf_gpu_acl *acl, const struct xsknf_gpu_acl_o
       live_k = static_cast<AclKey *>(malloc(sizeof(AclKey) * (keep ? keep : 1)));
       live_a = static_cast<int32_t *>(malloc(sizeof(int32_t) * (keep ? keep : 1)));
       if (!live_k || !live_a) throw std::bad_alloc();
+      if (acl->ctr) {
+        live_c = static_cast<AclCounter *>(malloc(sizeof(AclCounter) * (keep ? keep : 1)));
+        live_s = static_cast<uint32_t *>(malloc(sizeof(uint32_t) * (keep ? keep : 1)));
+        from = static_cast<uint32_t *>(malloc(sizeof(uint32_t) * slots));
+        if (!live_c || !live_s || !from) throw std::bad_alloc();
+      }
     } else {
       dirty.reserve(dels.size() + puts.size());
     }
   } catch (const std::bad_alloc &) {
-    free(live_k);
-    free(live_a);
+    drop();
     return -ENOMEM;
   }
   void *staged = nullptr;
 #ifndef XSKNF_ACL_HOST_ONLY
   xsknf_gpu::AclStage *stage = nullptr;
   if (acl->d_keys) {
-    const size_t bytes = rebuild ? (sizeof(AclKey) + sizeof(int32_t)) * static_cast<size_t>(slots)
+    // (with counters a rebuild sends the new slots' old slots behind the table)
+    const size_t bytes = rebuild ? (sizeof(AclKey) + sizeof(int32_t) + (acl->d_ctr ? sizeof(uint32_t) : 0)) * static_cast<size_t>(slots)
                                  : sizeof(xsknf_gpu::AclUpdateRec) * (dels.size() + puts.size());
-    const int rc = xsknf_gpu::acl_stage_acquire(acl, bytes, !rebuild, &stage, &staged);
+    int rc = xsknf_gpu::acl_stage_acquire(acl, bytes, !rebuild, &stage, &staged);
+    if (!rc && rebuild && acl->d_ctr) rc = xsknf_gpu::acl_counters_spare(acl);
     if (rc) {
-      free(live_k);
-      free(live_a);
+      drop();
       return rc;
     }
   }
@@ -413,15 +458,18 @@ int xsknf_gpu_acl_update(struct xsknf_gpu_acl *acl, const struct xsknf_gpu_acl_o
     --acl->probe_hist[probes];
     acl->keys[s] = kTombstone;
     acl->actions[s] = 0;
-    if (!rebuild) dirty.push_back(s);   // (reserved above)
+    if (acl->ctr) acl->ctr[s] = AclCounter{0, 0};
+    if (!rebuild) dirty.push_back(acl->ctr ? s | xsknf_gpu::kAclRecZero : s);   // (reserved above)
   }
   acl->rules -= static_cast<uint32_t>(dels.size());
   acl->tombstones += static_cast<uint32_t>(dels.size());
   while (acl->max_probe && !acl->probe_hist[acl->max_probe]) --acl->max_probe;
   if (rebuild) {
-    rebuild_in_place(acl, live_k, live_a);
+    rebuild_in_place(acl, live_k, live_a, live_c, live_s, from);
     free(live_k);
     free(live_a);
+    free(live_c);
+    free(live_s);
   }
   for (const uint32_t i : puts) {
     const AclKey k = key_of(ops[i].rule);
@@ -434,25 +482,50 @@ int xsknf_gpu_acl_update(struct xsknf_gpu_acl *acl, const struct xsknf_gpu_acl_o
       if (at.probes > acl->max_probe) acl->max_probe = at.probes;
     }
     acl->actions[at.slot] = ops[i].rule.action;
-    if (!rebuild) dirty.push_back(at.slot);
+    // a key new to the map starts at 0/0 (its slot held no live key: the counters
+    // there are 0 already, on the host), and so does one the call deleted first
+    const bool fresh = acl->ctr && (!at.found || again[i]);
+    if (fresh) {
+      acl->ctr[at.slot] = AclCounter{0, 0};
+      if (rebuild) from[at.slot] = kAclNone;
+    }
+    if (!rebuild) dirty.push_back(fresh ? at.slot | xsknf_gpu::kAclRecZero : at.slot);
   }
 
 #ifndef XSKNF_ACL_HOST_ONLY
   // Pass 3: the device table, on the stream.
-  if (!acl->d_keys) return 0;
+  if (!acl->d_keys) {
+    free(from);
+    return 0;
+  }
   if (rebuild) {
     memcpy(staged, acl->keys, sizeof(AclKey) * slots);
     memcpy(static_cast<char *>(staged) + sizeof(AclKey) * slots, acl->actions, sizeof(int32_t) * slots);
+    if (from) memcpy(static_cast<char *>(staged) + (sizeof(AclKey) + sizeof(int32_t)) * slots, from, sizeof(uint32_t) * slots);
+    free(from);
     return xsknf_gpu::acl_enqueue_table(acl, stage, stream);
   }
-  // a put may have taken a slot this call's delete left: each slot once, as it is now
-  std::sort(dirty.begin(), dirty.end());
-  dirty.erase(std::unique(dirty.begin(), dirty.end()), dirty.end());
+  // a put may have taken a slot this call's delete left: each slot once, as it is
+  // now.  (With counters an entry may carry kAclRecZero above its slot: ordered
+  // by the slot alone, a slot's entries or-ed into one.)
+  std::sort(dirty.begin(), dirty.end(), [](uint32_t x, uint32_t y) {
+    return (x & xsknf_gpu::kAclRecSlotMask) < (y & xsknf_gpu::kAclRecSlotMask);
+  });
+  size_t nd = 0;
+  for (size_t i = 0; i < dirty.size(); ++i) {
+    if (nd && ((dirty[nd - 1] ^ dirty[i]) & xsknf_gpu::kAclRecSlotMask) == 0) dirty[nd - 1] |= dirty[i];
+    else dirty[nd++] = dirty[i];
+  }
+  dirty.resize(nd);
   xsknf_gpu::AclUpdateRec *rec = static_cast<xsknf_gpu::AclUpdateRec *>(staged);
-  for (size_t i = 0; i < dirty.size(); ++i) rec[i] = xsknf_gpu::AclUpdateRec{dirty[i], acl->keys[dirty[i]], acl->actions[dirty[i]]};
+  for (size_t i = 0; i < dirty.size(); ++i) {
+    const uint32_t s = dirty[i] & xsknf_gpu::kAclRecSlotMask;
+    rec[i] = xsknf_gpu::AclUpdateRec{dirty[i], acl->keys[s], acl->actions[s]};
+  }
   return xsknf_gpu::acl_enqueue_records(acl, stage, static_cast<uint32_t>(dirty.size()), stream);
 #else
   (void)staged;
+  free(from);
   return 0;
 #endif
 }
@@ -479,6 +552,79 @@ int xsknf_gpu_acl_dump(const struct xsknf_gpu_acl *acl, int which, struct xsknf_
   free(tmp);
   return rc;
 #else
+  return -ENODEV;
+#endif
+}
+
+int xsknf_gpu_acl_counters_enable(struct xsknf_gpu_acl *acl) {
+  if (!acl) return -EINVAL;
+  if (acl->ctr) return 0;
+  // one allocation: the counters, then the totals
+  void *h = calloc(1, sizeof(AclCounter) * static_cast<size_t>(acl->slots) + sizeof(uint64_t) * XSKNF_GPU_ACL_TOTALS);
+  if (!h) return -ENOMEM;
+#ifndef XSKNF_ACL_HOST_ONLY
+  if (acl->d_keys) {
+    const int rc = xsknf_gpu::acl_counters_device_enable(acl);
+    if (rc) {
+      free(h);
+      return rc;
+    }
+  }
+#endif
+  acl->ctr = static_cast<AclCounter *>(h);
+  acl->totals = reinterpret_cast<uint64_t *>(acl->ctr + acl->slots);
+  return 0;
+}
+
+int xsknf_gpu_acl_counters_dump(const struct xsknf_gpu_acl *acl, int which, struct xsknf_gpu_acl_rule *rules_out,
+                                struct xsknf_gpu_acl_counter *counters_out, uint32_t cap, uint32_t *n_out,
+                                uint64_t *totals_out) {
+  if (!acl || !acl->ctr || !n_out || (cap && (!rules_out || !counters_out))) return -EINVAL;
+  if (which == XSKNF_GPU_ACL_HOST_TABLE) {
+    const int rc = dump_table(acl->keys, acl->actions, acl->slots, rules_out, cap, n_out, acl->ctr, counters_out);
+    if (totals_out && rc != -ENOMEM) memcpy(totals_out, acl->totals, sizeof(uint64_t) * XSKNF_GPU_ACL_TOTALS);
+    return rc;
+  }
+  if (which != XSKNF_GPU_ACL_DEVICE_TABLE) return -EINVAL;
+  if (!acl->d_keys) return -ENODEV;
+#ifndef XSKNF_ACL_HOST_ONLY
+  const size_t kb = sizeof(AclKey) * static_cast<size_t>(acl->slots), ab = sizeof(int32_t) * static_cast<size_t>(acl->slots);
+  const size_t cb = sizeof(AclCounter) * static_cast<size_t>(acl->slots);
+  char *tmp = static_cast<char *>(malloc(cb + kb + ab));   // (the counters first: 8-byte aligned)
+  if (!tmp) return -ENOMEM;
+  uint64_t tot[XSKNF_GPU_ACL_TOTALS];
+  hipError_t e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(tmp, acl->d_ctr, cb, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(tmp + cb, acl->d_keys, kb + ab, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(tot, acl->d_totals, sizeof(tot), hipMemcpyDeviceToHost);
+  int rc;
+  if (e == hipSuccess) {
+    rc = dump_table(reinterpret_cast<AclKey *>(tmp + cb), reinterpret_cast<int32_t *>(tmp + cb + kb), acl->slots, rules_out,
+                    cap, n_out, reinterpret_cast<AclCounter *>(tmp), counters_out);
+    if (totals_out && rc != -ENOMEM) memcpy(totals_out, tot, sizeof(tot));
+  } else {
+    xsknf_gpu::set_error(e, "ACL counters dump");
+    rc = -EIO;
+  }
+  free(tmp);
+  return rc;
+#else
+  return -ENODEV;
+#endif
+}
+
+int xsknf_gpu_acl_counters_clear(struct xsknf_gpu_acl *acl, int which, void *stream) {
+  if (!acl || !acl->ctr) return -EINVAL;
+  if (which == XSKNF_GPU_ACL_HOST_TABLE) {
+    memset(acl->ctr, 0, sizeof(AclCounter) * static_cast<size_t>(acl->slots) + sizeof(uint64_t) * XSKNF_GPU_ACL_TOTALS);
+    return 0;
+  }
+  if (which != XSKNF_GPU_ACL_DEVICE_TABLE) return -EINVAL;
+  if (!acl->d_keys) return -ENODEV;
+#ifndef XSKNF_ACL_HOST_ONLY
+  return xsknf_gpu::acl_counters_device_clear(acl, stream);
+#else
+  (void)stream;
   return -ENODEV;
 #endif
 }

@@ -28,6 +28,10 @@
 // the update's new keys leave one slot empty; an update that would pass either
 // limit rebuilds the table in place, tombstone-free, before it stores its puts.
 // A probe therefore looks at no more than live keys + tombstones + 1 slots.
+//
+// Hit counters (include/xsknf_gpu.h xsknf_gpu_acl_counters_*) are a side array:
+// one AclCounter per slot, in the object only once it has been asked for.  The
+// key slots and the actions keep their layout; counters[s] belongs to keys[s].
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -49,12 +53,30 @@ constexpr uint32_t kAclTombstoneShare = 4;   // at most slots / 4 tombstones out
 // writes them, kernel_acl_update.h scatters them).  The records of one update
 // name each slot AT MOST ONCE and carry its final state: the scatter's lanes
 // store without looking at one another.
+//
+// An object with counters sets kAclRecZero in `slot` where the slot's counters
+// start again at 0/0: the slot became a tombstone, or its key is new to the map
+// (also a key deleted and put again by the same call, which the device could
+// not tell from one that stayed).  Slot numbers stay below 2^24
+// (XSKNF_GPU_ACL_MAX_SLOTS), so the bit is free; an object without counters
+// never sets it.
 struct AclUpdateRec {
   uint32_t slot;
   AclKey key;
   int32_t action;
 };
 static_assert(sizeof(AclUpdateRec) == 24 && alignof(AclUpdateRec) == 4, "three 8-byte loads per record");
+constexpr uint32_t kAclRecZero = 1u << 31;
+constexpr uint32_t kAclRecSlotMask = ~kAclRecZero;
+
+// One slot's hit counters: the frames that found the slot's key and the sum of
+// their descriptors' len.
+struct AclCounter {
+  uint64_t packets, bytes;
+};
+static_assert(sizeof(AclCounter) == 16, "two 8-byte adds per group of hits");
+// totals (XSKNF_GPU_ACL_TOTALS)
+enum AclTotal : int { kAclFrames, kAclHits, kAclMisses, kAclDecided, kAclTotals };
 
 XSKNF_HD inline uint32_t acl_hash(uint32_t a, uint32_t b, uint32_t c, uint32_t p) {
   uint32_t h = a * 0x9E3779B1u;
@@ -113,6 +135,19 @@ struct xsknf_gpu_acl {
   uint32_t tombstones;         // slots that hold the tombstone
   uint32_t *probe_hist;        // host, slots + 1 entries: [d] = live keys found at their d-th probe (max_probe's source)
   struct xsknf_gpu_acl_staging *staging;   // acl_update_device.hip: the updates' buffers (NULL until the first one)
+  // hit counters (all NULL / 0 until xsknf_gpu_acl_counters_enable).  Host: one
+  // allocation, `slots` counters and behind them the totals.  Device: the same
+  // in d_ctr_base; a rebuild gathers the counters into the other of two arrays
+  // (d_ctr_spare, allocated by the first such rebuild together with d_ctr_map,
+  // the new slots' old slots) and the two change roles
+  xsknf_gpu::AclCounter *ctr;
+  uint64_t *totals;
+  xsknf_gpu::AclCounter *d_ctr;
+  uint64_t *d_totals;
+  xsknf_gpu::AclCounter *d_ctr_spare;
+  uint32_t *d_ctr_map;
+  void *d_ctr_base, *d_ctr_spare_base;
+  uint64_t d_ctr_bytes;                    // device memory of the above, part of device_bytes
 };
 
 #ifndef XSKNF_ACL_HOST_ONLY
@@ -130,5 +165,14 @@ int acl_enqueue_records(xsknf_gpu_acl *acl, AclStage *stage, uint32_t n, void *s
 // the whole table at the stage's start, keys then actions: copy it over the device table
 int acl_enqueue_table(xsknf_gpu_acl *acl, AclStage *stage, void *stream);
 int acl_staging_release(xsknf_gpu_acl *acl);   // _destroy
+// Counters.  _enable: the device arrays, zeroed.  _spare: the second array and
+// the map, before a rebuild's host pass (nothing after it may fail for want of
+// memory).  acl_enqueue_table of an object with counters expects the map, one
+// uint32_t per slot, behind the table in the stage and enqueues the copy, the
+// gather and the arrays' change of roles with it.
+int acl_counters_device_enable(xsknf_gpu_acl *acl);
+int acl_counters_spare(xsknf_gpu_acl *acl);
+int acl_counters_device_clear(xsknf_gpu_acl *acl, void *stream);
+int acl_counters_device_release(xsknf_gpu_acl *acl);
 }  // namespace xsknf_gpu
 #endif

@@ -10,10 +10,18 @@
 //            (+ 4 B on a hit) of the table read, 4 B verdict written per frame.
 // The UMEM is only read.  A translation unit of its own: none of the
 // checksummer's kernels is rebuilt for it.
+// An ACL with hit counters (xsknf_gpu_acl_counters_enable) takes the counting
+// twin of that launch instead (kernel_firewall_count.h): the same reads, and
+// per block two 8-byte atomic adds for every distinct rule its frames hit.
 #include <errno.h>
+#ifdef XSKNF_AB
+#include <stdlib.h>
+#include <string.h>
+#endif
 
 #include "checksummer_internal.h"
 #include "kernel_firewall.h"
+#include "kernel_firewall_count.h"
 
 extern "C" {
 
@@ -41,7 +49,24 @@ int xsknf_gpu_firewall_batch(const uint8_t *umem, uint64_t umem_size, const stru
   a.slots = acl->slots;
   const uint32_t tiles = n / firewall::kThreads + (n % firewall::kThreads != 0);   // (no sum that can wrap)
   const dim3 grid(tiles < static_cast<uint32_t>(firewall::kMaxBlocks) ? tiles : firewall::kMaxBlocks);
-  hipLaunchKernelGGL(firewall::firewall_lookup, grid, dim3(firewall::kThreads), 0, static_cast<hipStream_t>(stream), a);
+  if (acl->d_ctr) {
+    const firewall::CountArgs c = {a, acl->d_ctr, reinterpret_cast<unsigned long long *>(acl->d_totals)};
+    const hipStream_t hs = static_cast<hipStream_t>(stream);
+#ifdef XSKNF_AB
+    // XSKNF_ACL_COUNT_SHAPE=naive|wave|stage: the shapes the product's is compared with (kernel_firewall_count.h)
+    static const char *const shape_env = getenv("XSKNF_ACL_COUNT_SHAPE");
+    static const int shape = !shape_env ? firewall::kStageRepeats : !strcmp(shape_env, "naive") ? firewall::kNaive
+                             : !strcmp(shape_env, "wave") ? firewall::kWave
+                             : !strcmp(shape_env, "stage") ? firewall::kStageAll : firewall::kStageRepeats;
+    if (shape == firewall::kNaive) hipLaunchKernelGGL(firewall::firewall_lookup_count<firewall::kNaive>, grid, dim3(firewall::kThreads), 0, hs, c);
+    else if (shape == firewall::kWave) hipLaunchKernelGGL(firewall::firewall_lookup_count<firewall::kWave>, grid, dim3(firewall::kThreads), 0, hs, c);
+    else if (shape == firewall::kStageAll) hipLaunchKernelGGL(firewall::firewall_lookup_count<firewall::kStageAll>, grid, dim3(firewall::kThreads), 0, hs, c);
+    else
+#endif
+    hipLaunchKernelGGL(firewall::firewall_lookup_count<firewall::kStageRepeats>, grid, dim3(firewall::kThreads), 0, hs, c);
+  } else {
+    hipLaunchKernelGGL(firewall::firewall_lookup, grid, dim3(firewall::kThreads), 0, static_cast<hipStream_t>(stream), a);
+  }
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     set_error(e, "device firewall");

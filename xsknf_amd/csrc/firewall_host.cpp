@@ -27,6 +27,10 @@ int xsknf_gpu_firewall_host(const uint8_t *umem, uint64_t umem_size, const struc
                             const struct xsknf_gpu_acl *acl, int32_t *verdicts) {
   if (!acl) return -EINVAL;
   if (n && (!umem || !descs || !verdicts)) return -EINVAL;
+  // the ACL's host counters, if it has any (xsknf_gpu_acl_counters_enable): the
+  // hits per slot, and the totals from the hits and the frames that reached the map
+  xsknf_gpu::AclCounter *ctr = acl->ctr;
+  uint64_t hits = 0, looked = 0;
   for (uint32_t i = 0; i < n; ++i) {
     const uint64_t off = xsknf_gpu::desc_offset(descs[i].addr);
     const uint32_t len = descs[i].len;
@@ -46,8 +50,26 @@ int xsknf_gpu_firewall_host(const uint8_t *umem, uint64_t umem_size, const struc
       continue;
     }
     if (next + (proto == 6 ? 20u : 8u) > len) continue;
-    verdicts[i] = xsknf_gpu::acl_lookup(acl->keys, acl->actions, acl->slots, le32(f + 26), le32(f + 30),
-                                        le32(f + next), proto);   // rules 6, 7
+    if (!ctr) {
+      verdicts[i] = xsknf_gpu::acl_lookup(acl->keys, acl->actions, acl->slots, le32(f + 26), le32(f + 30),
+                                          le32(f + next), proto);   // rules 6, 7
+      continue;
+    }
+    const uint32_t s = xsknf_gpu::acl_find(acl->keys, acl->slots, le32(f + 26), le32(f + 30), le32(f + next), proto);
+    ++looked;
+    verdicts[i] = 0;
+    if (s != xsknf_gpu::kAclNone) {
+      verdicts[i] = acl->actions[s];
+      ++ctr[s].packets;
+      ctr[s].bytes += len;
+      ++hits;
+    }
+  }
+  if (ctr) {
+    acl->totals[xsknf_gpu::kAclFrames] += n;
+    acl->totals[xsknf_gpu::kAclHits] += hits;
+    acl->totals[xsknf_gpu::kAclMisses] += looked - hits;
+    acl->totals[xsknf_gpu::kAclDecided] += n - looked;
   }
   return 0;
 }

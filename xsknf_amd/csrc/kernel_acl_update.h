@@ -18,6 +18,7 @@ struct Args {
   int32_t *actions;
   uint32_t n;
   uint32_t slots;
+  AclCounter *counters;   // the object's hit counters, or NULL: then `slot` carries no flag
 };
 
 // One lane per record; a block takes kThreads consecutive records per step and
@@ -33,16 +34,41 @@ struct Args {
 // record whose slot is not below `slots` is skipped.  The two stores of a slot
 // are not one: a lookup that runs beside the scatter may see the new key with
 // the old action (include/xsknf_gpu.h leaves that to the caller's ordering).
+// With counters the record's kAclRecZero says that the slot's counters start
+// again (acl_table.h): one more 16-byte store, to the same lane's own slot.
 // No LDS, no atomics, no block waits on another.
 __global__ __launch_bounds__(kThreads) void acl_scatter(const Args a) {
   const uint32_t stride = gridDim.x * kThreads;
   for (uint64_t r = blockIdx.x * kThreads + threadIdx.x; r < a.n; r += stride) {
     const uint2 w0 = a.recs[3 * r], w1 = a.recs[3 * r + 1], w2 = a.recs[3 * r + 2];
-    const uint32_t slot = w0.x;
+    const uint32_t slot = a.counters ? w0.x & kAclRecSlotMask : w0.x;
     if (slot < a.slots) {
       *reinterpret_cast<uint4 *>(a.keys + slot) = make_uint4(w0.y, w1.x, w1.y, w2.x);
       a.actions[slot] = static_cast<int32_t>(w2.y);
+      if (a.counters && (w0.x & kAclRecZero)) *reinterpret_cast<uint4 *>(a.counters + slot) = make_uint4(0, 0, 0, 0);
     }
+  }
+}
+
+// A rebuild's carry: the table's new slot s holds the key that lay in slot
+// from[s], or (kAclNone) a key new to the map or none.  One lane per slot:
+// 4 bytes of the map read and 16 bytes of `to` written, both coalesced, and for
+// a carried key 16 bytes of `cur` read from wherever it lay.  `to` and `cur`
+// are different arrays, so the order of lanes means nothing; an old slot that is
+// not below `slots` counts as none.
+struct GatherArgs {
+  const uint32_t *from;
+  const AclCounter *cur;
+  AclCounter *to;
+  uint32_t slots;
+};
+__global__ __launch_bounds__(kThreads) void acl_counters_gather(const GatherArgs a) {
+  const uint32_t stride = gridDim.x * kThreads;
+  for (uint64_t s = blockIdx.x * kThreads + threadIdx.x; s < a.slots; s += stride) {
+    const uint32_t old = a.from[s];
+    uint4 c = make_uint4(0, 0, 0, 0);
+    if (old < a.slots) c = *reinterpret_cast<const uint4 *>(a.cur + old);
+    *reinterpret_cast<uint4 *>(a.to + s) = c;
   }
 }
 

@@ -61,6 +61,7 @@
 #include <stdint.h>
 
 #include "desc_rules.h"
+#include "kernel_acl_count.h"
 #include "lb_table.h"
 #include "ld_bytes.h"
 
@@ -170,6 +171,13 @@ __device__ __forceinline__ void flush(const Args &a, uint32_t *c) {
 // only the frame's own sid and the immutable ACL, so it needs no order.  The
 // two probes run one after the other: a variant that issued the ACL's and the
 // session table's home-slot loads together measured no faster.
+// An ACL with hit counters (a.gate.counters) counts the frame here, at the one
+// place a gated frame is decided -- the later launches, the ordered path among
+// them, see it as kDone -- with the firewall's combine: the candidates of a
+// wave are at the probe together, the lanes the parse decided have left for
+// the loop's next trip and are in nobody's group.  The ACL's totals come from
+// the block's own counts when it flushes: in this launch kPassed and kDropped
+// are exactly the frames decided before the lookup.
 // The load balancer's instantiation, kGate false, carries none of this.
 template <bool kGate>
 __global__ __launch_bounds__(kThreads) void lb_propose(const Args a) {
@@ -210,6 +218,7 @@ __global__ __launch_bounds__(kThreads) void lb_propose(const Args a) {
     const lb::Key sid = {sa, da, ld_bytes(a.umem, off + next, 4), proto};    // rule 6
     if constexpr (kGate) {
       const uint32_t g = acl_find(a.gate.keys, a.gate.slots, sid.a, sid.b, sid.c, sid.p);
+      if (a.gate.counters) acl_count::count_hits(a.gate.counters, g != kAclNone, g, len);
       if (g != kAclNone) {                                                   // rule 6a
         count(c, lb::kGated);
         a.verdicts[f] = a.gate.actions[g];
@@ -249,6 +258,15 @@ __global__ __launch_bounds__(kThreads) void lb_propose(const Args a) {
     a.state[f] = kProposer | shape;
   }
   flush(a, c);
+  if constexpr (kGate) {
+    if (a.gate.counters && threadIdx.x < kAclTotals) {   // (flush's barrier stands before this)
+      const uint32_t decided = c[lb::kPassed] + c[lb::kDropped];
+      const uint32_t t = threadIdx.x == kAclFrames ? c[lb::kFrames] : threadIdx.x == kAclHits ? c[lb::kGated]
+                         : threadIdx.x == kAclDecided ? decided : c[lb::kFrames] - c[lb::kGated] - decided;
+      if (t) __hip_atomic_fetch_add(&a.gate.totals[threadIdx.x], static_cast<unsigned long long>(t), __ATOMIC_RELAXED,
+                                    __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
 }
 
 // `nb` = 2 or 4 bytes of v at pos: 2-byte stores at even addresses, else bytes.

@@ -148,7 +148,10 @@ int xsknf_gpu_lbfw_batch(uint8_t *umem, uint64_t umem_size, const struct xsknf_g
     set_error_text("the ACL was created without a device: it serves xsknf_gpu_lbfw_host only");
     return -ENODEV;
   }
-  const lb::Gate gate = acl ? lb::Gate{acl->d_keys, acl->d_actions, acl->slots} : lb::Gate{nullptr, nullptr, 0};
+  // (d_ctr / d_totals: the ACL's hit counters, NULL unless enabled)
+  const lb::Gate gate = acl ? lb::Gate{acl->d_keys, acl->d_actions, acl->slots, acl->d_ctr,
+                                       reinterpret_cast<unsigned long long *>(acl->d_totals)}
+                            : lb::Gate{nullptr, nullptr, 0, nullptr, nullptr};
   return run_batch(umem, umem_size, descs, n, ingress_ifindex, lb::lbfw_pass_verdict(ingress_ifindex, num_interfaces),
                    gate, lb, verdicts, workspace, workspace_bytes, stats_dev, stream, "device lbfw");
 }

@@ -325,10 +325,14 @@ enum Stat : int { kFrames, kRewritten, kPassed, kDropped, kCreated, kFailed, kOr
 // The lbfw NF's gate (rule 6a): an ACL table (acl_table.h) on the host or the
 // device.  keys == nullptr: no gate -- the load balancer, and lbfw with
 // acl == NULL.
+// counters / totals: the ACL's hit counters (include/xsknf_gpu.h
+// xsknf_gpu_acl_counters_*), or NULL: no counting.
 struct Gate {
   const AclKey *keys;
   const int32_t *actions;
   uint32_t slots;
+  AclCounter *counters;
+  unsigned long long *totals;
 };
 
 // One frame of the reference's loop against the tables, the inserts included;
@@ -354,8 +358,14 @@ XSKNF_HD inline int32_t frame(const Tables &t, const Gate &gate, uint8_t *f, uin
     const uint32_t g = acl_find(gate.keys, gate.slots, sid.a, sid.b, sid.c, sid.p);
     if (g != kAclNone) {
       ++stats[kGated];
+      if (gate.counters) {   // (the host model; on the device lb_propose<true> has counted the frame)
+        ++gate.counters[g].packets;
+        gate.counters[g].bytes += len;
+        ++gate.totals[kAclHits];
+      }
       return gate.actions[g];
     }
+    if (gate.counters) ++gate.totals[kAclMisses];
   }
   Val rep;
   const uint32_t s = find(t.keys, t.slots, sid);

@@ -24,7 +24,9 @@ int xsknf_gpu_lbfw_host(uint8_t *umem, uint64_t umem_size, const struct xsknf_gp
   uint64_t st[lb::kStats] = {0};
   const lb::Tables t = {lb->svc,       lb->bk,    lb->keys,         lb->vals,   &lb->count,
                         lb->svc_slots, lb->slots, lb->max_sessions, lb->stamps, &lb->clock};   // (stamps: rule 11, or NULL)
-  const lb::Gate gate = acl ? lb::Gate{acl->keys, acl->actions, acl->slots} : lb::Gate{nullptr, nullptr, 0};
+  const lb::Gate gate = acl ? lb::Gate{acl->keys, acl->actions, acl->slots, acl->ctr, reinterpret_cast<unsigned long long *>(acl->totals)}
+                            : lb::Gate{nullptr, nullptr, 0};
+  const uint64_t hits0 = acl && acl->ctr ? acl->totals[kAclHits] : 0, misses0 = acl && acl->ctr ? acl->totals[kAclMisses] : 0;
   const int32_t pass = lb::lbfw_pass_verdict(ingress_ifindex, num_interfaces);
   st[lb::kFrames] = n;
   for (uint32_t i = 0; i < n; ++i) {
@@ -36,6 +38,10 @@ int xsknf_gpu_lbfw_host(uint8_t *umem, uint64_t umem_size, const struct xsknf_gp
       continue;
     }
     verdicts[i] = lb::frame(t, gate, umem + off, len, ingress_ifindex, pass, st);
+  }
+  if (acl && acl->ctr) {   // (lb::frame counted the hits and the misses at the gate)
+    acl->totals[kAclFrames] += n;
+    acl->totals[kAclDecided] += n - (acl->totals[kAclHits] - hits0) - (acl->totals[kAclMisses] - misses0);
   }
   if (stats)
     for (int k = 0; k < lb::kStats; ++k) stats[k] = st[k];

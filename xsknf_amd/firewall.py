@@ -9,7 +9,10 @@ rules per frame are in include/xsknf_gpu.h ("the firewall NF").
 `Acl` holds the table (xsknf_gpu_acl_*: xsknf_amd/csrc/acl.cpp), on the host and
 on the device that was current when it was made; `Acl.update` puts, replaces
 and deletes rules of the live table, on the device in stream order
-(xsknf_gpu_acl_update).  `firewall_batch` gives the
+(xsknf_gpu_acl_update); `Acl.counters_enable` gives every rule packet and byte
+counters, one set for the host calls and one for the device calls, which
+`Acl.counters` reads and `Acl.counters_clear` zeroes
+(xsknf_gpu_acl_counters_*).  `firewall_batch` gives the
 verdicts on the device for a UMEM and descriptors that lie there
 (xsknf_gpu_firewall_batch; xsknf_amd/csrc/firewall_device.hip), `firewall_host`
 on one CPU thread (xsknf_gpu_firewall_host: the model the device is held to).
@@ -39,6 +42,9 @@ OP_DTYPE = np.dtype([("rule", RULE_DTYPE), ("op", "<u4")])
 assert OP_DTYPE.itemsize == 24
 HOST_TABLE = _lib.ACL_HOST_TABLE
 DEVICE_TABLE = _lib.ACL_DEVICE_TABLE
+# struct xsknf_gpu_acl_counter: one rule's hits
+COUNTER_DTYPE = np.dtype([("packets", "<u8"), ("bytes", "<u8")])
+TOTALS = _lib.ACL_TOTALS    # frames, hits, misses, decided before the lookup
 
 
 def make_ops(rules, op) -> np.ndarray:
@@ -159,6 +165,45 @@ class Acl:
             _lib.check(lib.xsknf_gpu_acl_dump(self.handle, which, rules.ctypes.data, rules.size, ctypes.byref(n)),
                        "xsknf_gpu_acl_dump")
         return rules
+
+    def counters_enable(self) -> None:
+        """xsknf_gpu_acl_counters_enable: per-rule packet and byte counters and
+        four totals from now on, one set on the host and one on the device
+        (with no batch and no update in flight; idempotent)."""
+        _lib.check(_lib.load().xsknf_gpu_acl_counters_enable(self.handle), "xsknf_gpu_acl_counters_enable")
+
+    def counters(self, device: bool = False):
+        """xsknf_gpu_acl_counters_dump: (rules, counters, totals) of the host set
+        or (waiting for the device) the device set -- RULE_DTYPE records in
+        dump()'s order, COUNTER_DTYPE records that belong to them one by one,
+        and TOTALS uint64: frames, hits, misses, decided before the lookup."""
+        lib = _lib.load()
+        which = DEVICE_TABLE if device else HOST_TABLE
+        n = ctypes.c_uint32(0)
+        rc = lib.xsknf_gpu_acl_counters_dump(self.handle, which, None, None, 0, ctypes.byref(n), None)
+        if rc not in (0, -errno.ENOSPC):
+            _lib.check(rc, "xsknf_gpu_acl_counters_dump")
+        rules = np.zeros(int(n.value), dtype=RULE_DTYPE)
+        ctr = np.zeros(int(n.value), dtype=COUNTER_DTYPE)
+        totals = np.zeros(TOTALS, dtype=np.uint64)
+        _lib.check(lib.xsknf_gpu_acl_counters_dump(self.handle, which, rules.ctypes.data if rules.size else None,
+                                                   ctr.ctypes.data if rules.size else None, rules.size, ctypes.byref(n),
+                                                   totals.ctypes.data), "xsknf_gpu_acl_counters_dump")
+        return rules, ctr, totals
+
+    def counters_clear(self, device: bool = False, stream=None) -> None:
+        """xsknf_gpu_acl_counters_clear: zero the host set at once, or the device
+        set in the order of `stream` (as in update(): by default the current
+        torch stream of the current device)."""
+        s = 0
+        if device:
+            if stream is None:
+                import torch
+                s = torch.cuda.current_stream().cuda_stream
+            else:
+                s = int(getattr(stream, "cuda_stream", stream))
+        _lib.check(_lib.load().xsknf_gpu_acl_counters_clear(self.handle, DEVICE_TABLE if device else HOST_TABLE,
+                                                            ctypes.c_void_p(s or None)), "xsknf_gpu_acl_counters_clear")
 
     def close(self) -> None:
         if self._h:
